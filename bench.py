@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Chemeleon reverse-diffusion sampling path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,12 +19,22 @@ Weights: the seeded synthetic recipe of the real architecture (hidden 512,
 6 layers, 128 frequencies, fc edges); conditioning: seeded vectors broadcast
 from rank 0 (RCCL), standing in for the frozen text encoder's output.
 
-One JSON line is printed by rank 0, including:
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0)
+with the headline: metric, value, unit, higher_is_better, dtype, ms_per_step and the
+workload's configuration. --dump-outputs DIR also writes the state after the last
+timed step (what a caller iterating the sampling path receives) as float32
+DIR/atom_types.npy [N], DIR/frac_coords.npy [N, 3] and DIR/lattices.npy [B, 3, 3]; the
+inputs are seeded, so equal arguments give equal inputs from run to run.
+
+--full adds every other leg, each a run of its own after the timed region:
   roofline     — the dominant kernel (edge message GEMM) against fp32 MFMA peak,
                  timed live with HIP events on its launch stream;
   msgpass      — the message-passing aggregation kernel against HBM peak;
   cpu_baseline — the CPU oracle (a restatement of the reference PyTorch CPU
-                 path) timed on this host on a bounded sample (rank 0, N=1).
+                 path) timed on this host on a bounded sample (rank 0, N=1);
+  api          — Chemeleon.sample() end to end and the parity-mode (noise='torch') steps;
+  edge_events  — the edge kernels' health counters.
+--no-cpu-baseline, --no-api-legs and --no-traffic prune legs of a --full run.
 """
 
 import argparse
@@ -58,6 +68,13 @@ def parse():
     p.add_argument("--n-samples", type=int, default=512, help="total samples across all ranks")
     p.add_argument("--n-atoms", type=int, default=40)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: per-kernel roofline (instrumented eager "
+                        "passes), in-run HBM traffic, the standalone aggregation kernel, the API legs, the CPU "
+                        "baseline and the edge kernels' health counters (off: the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the state after the last timed step as float32 DIR/atom_types.npy, "
+                        "DIR/frac_coords.npy and DIR/lattices.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-samples", type=int, default=64)
     p.add_argument("--cpu-steps", type=int, default=3)
@@ -86,7 +103,10 @@ def parse():
                         "share's structures")
     p.add_argument("--share-rank", type=int, default=0)
     p.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)  # (the PMC passes' workload)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.steps + args.warmup > T_STEPS:
+        p.error(f"need --steps >= 1, --warmup >= 0 and --steps + --warmup <= {T_STEPS} (one sample's timesteps)")
+    return args
 
 
 def edge_layer_bytes(natoms, P=2, pairs=None):
@@ -342,6 +362,184 @@ def traffic_probe(args):
     torch.cuda.synchronize()
 
 
+def dump_outputs(path, final):
+    """--dump-outputs: the state after the last timed step (atom types, fractional coordinates, lattices)
+    as float32 .npy files (atom types are class indices below 104, exact in float32)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in zip(("atom_types", "frac_coords", "lattices"), final):
+        np.save(os.path.join(path, name + ".npy"), v.detach().cpu().numpy().astype(np.float32))
+
+
+def full_legs(args, model, dev, dist, rank, world, natoms, total, cond, null, node_base, g0, init, s_per_step, value,
+              math, draw_ms, draw_ms_8):
+    """--full: every leg besides the headline, run after the timed region; returns their entries of the
+    result line."""
+    from chemeleon_amd import _lib
+    if not args.no_graph:
+        # the timed steps replayed a captured graph: time the kernels with HIP events in an
+        # instrumented eager pass of 2 reverse steps on the same shapes, right after the timed region
+        _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
+        it2 = model.sample_states(natoms, None, 2.0, 1e-5, noise="philox", seed=args.seed, text_embeds=cond,
+                                  null_text_embeds=null, clone=False, node_base=node_base, graph_base=g0,
+                                  init=init, t_stop=998, graph=False)
+        for _ in it2:
+            pass
+        torch.cuda.synchronize()
+    # the dominant kernel: both edge layers in one grid (k_edge16_layer, the default on fc batches) or,
+    # when that is off, the edge message GEMM; with the one-grid kernel on, a second eager pass times the
+    # two layers as separate launches for context
+    nlay, ms_lay = _lib.prof_read(_lib.K_EDGE_LAYER)
+    ndec, ms_dec = _lib.prof_read(_lib.K_DECODER)
+    if nlay:
+        _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
+        model.decoder.set_option("edge_layer", 0)
+        it3 = model.sample_states(natoms, None, 2.0, 1e-5, noise="philox", seed=args.seed, text_embeds=cond,
+                                  null_text_embeds=null, clone=False, node_base=node_base, graph_base=g0,
+                                  init=init, t_stop=998, graph=False)
+        for _ in it3:
+            pass
+        torch.cuda.synchronize()
+        model.decoder.set_option("edge_layer", 1)
+    _lib.check(_lib.load().chm_prof_enable(0), "prof_disable")
+    torch.cuda.synchronize()
+    events = _lib.prof_events()
+    if dist is not None:
+        ev = torch.tensor([events[k] for k in _lib.EVENT_NAMES], device=dev, dtype=torch.float64)
+        dist.all_reduce(ev)  # (summed over ranks)
+        events = {k: int(v) for k, v in zip(_lib.EVENT_NAMES, ev.tolist())}
+
+    # live per-kernel timing (HIP events on the launch stream)
+    nmsg, ms_msg = _lib.prof_read(_lib.K_EDGE_MESSAGE)
+    nfou, ms_fou = _lib.prof_read(_lib.K_EDGE_FOURIER)
+    E = sum(n * n for n in natoms)
+    N = sum(natoms)
+    msg_flops = 2.0 * (2 * E) * H * H  # one launch covers both conditionings
+    msg_tflops = msg_flops / (ms_msg / nmsg * 1e-3) / 1e12 if nmsg else None
+    seg_bytes = 2.0 * (E * H * 4 + N * H * 4)
+    step_flops = 2 * decoder_pair_flops(natoms)
+    Ep = sum(n * (n + 1) // 2 for n in natoms)
+    fou_flops = 2.0 * (Ep if edge_pairs_on() else E) * 768 * H  # edge layer 1: D.f once for both conditionings
+    # (on pairs: once per unordered pair, k_edge16_pairs)
+    fou_tflops = fou_flops / (ms_fou / nfou * 1e-3) / 1e12 if nfou else None
+    msg_kernel = ((pairs_layer_kernel() or "k_edge16_pairs") if edge_pairs_on() else "k_edge16_layer") if nlay \
+        else "k_edge16<2"
+    traffic, traffic_src = None, "not collected for the ragged workload" if args.ragged else "not collected"
+    if math == "split16" and not args.ragged:
+        if rank == 0 and world == 1 and not args.no_traffic:
+            try:
+                traffic, traffic_src = measure_traffic(args, msg_kernel)
+            except Exception as e:  # noqa: BLE001
+                traffic, traffic_src = None, {"error": repr(e)}
+        if traffic is None and (args.n_samples, args.n_atoms, world) == (512, 40, 1):  # (the stored profile's shape)
+            failed = traffic_src
+            traffic, traffic_src = _stored_traffic(msg_kernel)
+            if traffic_src is not None:
+                traffic_src["in_run"] = failed if not args.no_traffic and world == 1 else "skipped"
+    lay_flops = fou_flops + msg_flops
+    lay_tflops = lay_flops / (ms_lay / nlay * 1e-3) / 1e12 if nlay else None
+    # fp32-equivalent ceilings: bf16x3 = 2.5 PF / 6 products; split16 edge GEMMs = 2.5 PF (fp16 dense
+    # = bf16 rate) / 3 products; f32 = the fp32 MFMA peak
+    peak = {"bf16x3": BF16X3_PEAK_TFLOPS, "split16": MFMA_BF16_PEAK_TFLOPS / 3}.get(math, MFMA_F32_PEAK_TFLOPS)
+
+    # standalone message-passing aggregation kernel (chm_segment_mean) on the
+    # bench batch's edge layout, [2, E, 512] fp32 messages (HIP events)
+    seg_gbs = seg_ms = None
+    try:
+        b = model.decoder.hip_batch(natoms, 2)
+        msg = torch.empty(2, b.num_edges, H, device=dev).normal_()
+        agg = torch.empty(2, b.num_nodes, H, device=dev)
+        L_ = _lib.load()
+        st = _lib.stream_handle(dev)
+        for _ in range(2):
+            _lib.check(L_.chm_segment_mean(b.handle, 2, _lib.ptr(msg), msg.numel(), _lib.ptr(agg), agg.numel(), st), "segment_mean")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            _lib.check(L_.chm_segment_mean(b.handle, 2, _lib.ptr(msg), msg.numel(), _lib.ptr(agg), agg.numel(), st), "segment_mean")
+        e1.record()
+        torch.cuda.synchronize()
+        seg_ms = e0.elapsed_time(e1) / 10
+        seg_gbs = seg_bytes / (seg_ms * 1e-3) / 1e9
+        del msg, agg
+    except Exception as e:  # noqa: BLE001
+        print("segment_mean microbench failed:", repr(e), file=sys.stderr)
+
+    out = {
+        "roofline": {"bound": "mfma",
+                     "timing": ("HIP events on the launch stream, eager pass of 2 steps after the timed graph replays"
+                                if not args.no_graph else "HIP events on the launch stream over warm-up + timed steps"),
+                     "kernel": {"split16": ((f"both edge layers of a CSP layer in one grid, layer 1 on "
+                                             f"unordered pairs ({msg_kernel}: D.f once per pair i <= j, both "
+                                             "directions' S = SiLU(U +- V + P + Q); S.W2^T + SiLU + fused "
+                                             "scatter_mean; 16x16x32 MFMA), both conditionings, incl. its two repair "
+                                             "launches (no-ops unless a check fails)") if edge_pairs_on() else
+                                            ("both edge layers of a CSP layer in one grid (k_edge16_layer: D.f + P_i + "
+                                             "Q_j + SiLU -> S, S.W2^T + SiLU + fused scatter_mean; 16x16x32 MFMA), "
+                                             "both conditionings, incl. its two repair launches (no-ops unless a "
+                                             "check fails)")) if nlay else
+                                           (f"edge message GEMM + fused scatter_mean ({msg_kernel}, EPI_SEGMEAN, "
+                                            "16x16x32 MFMA), both conditionings"),
+                                "bf16x3": "edge message GEMM + fused scatter_mean (k_gemm3_big<EPI_SEGMEAN>), "
+                                          "both conditionings",
+                                "f32": "edge message GEMM (k_gemm, S.W2^T + SiLU, both conditionings)"}[math],
+                     "achieved": lay_tflops if nlay else msg_tflops, "peak": peak, "unit": "TFLOP/s",
+                     "frac": ((lay_tflops if nlay else msg_tflops) / peak) if (lay_tflops or msg_tflops) else None,
+                     "traffic": traffic,
+                     "traffic_source": traffic_src,
+                     "mfma_busy": (traffic_src.get("mfma_busy") if isinstance(traffic_src, dict) else None),
+                     "mfma_busy_note": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), in-run PMC "
+                                       "pass over the same probe as traffic",
+                     "traffic_algorithmic": (edge_layer_bytes(natoms) if nlay else message_layer_bytes(natoms)),
+                     "peak_note": {"bf16x3": "fp32-equivalent flops; bf16 dense MFMA 2.5 PF / 6 products",
+                                   "split16": "fp32-equivalent flops (3 fp16 MFMA products each); fp16 dense MFMA "
+                                           "2.5 PF / 3 products",
+                                   "f32": "fp32 MFMA dense peak"}[math],
+                     "flops_per_launch": lay_flops if nlay else msg_flops, "launches": nlay or nmsg,
+                     "avg_ms": (ms_lay / nlay) if nlay else (ms_msg / nmsg if nmsg else None)},
+        "msgpass": {"bound": "hbm", "kernel": "k_segment_mean (standalone scatter_mean, chm_segment_mean)",
+                    "achieved": seg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": (seg_gbs / HBM_PEAK_GBS) if seg_gbs else None, "bytes_per_launch": seg_bytes,
+                    "avg_ms": seg_ms,
+                    "note": ("in the sampler the aggregation is fused into the message GEMM epilogue; this is the "
+                             "standalone kernel on the same [2,E,512] shape" if math != "f32" else
+                             "the kernel as launched by the sampler")},
+        "edge_layer2": {"kernel": "edge layer 2 alone (k_edge16<2>: S.W2^T + SiLU + fused scatter_mean), both "
+                                  "conditionings" + (" (second eager pass, two launches per layer)" if nlay else ""),
+                        "achieved": msg_tflops, "peak": peak, "unit": "TFLOP/s",
+                        "frac": (msg_tflops / peak) if msg_tflops else None, "flops_per_launch": msg_flops,
+                        "avg_ms": ms_msg / nmsg if nmsg else None},
+        "edge_layer1": {"kernel": ("edge layer 1 on unordered pairs (k_edge16_pairs: D.f once per pair i <= j, both "
+                                   "directions' S = SiLU(U +- V + P + Q) written split), both conditionings"
+                                   if edge_pairs_on() else
+                                   "edge layer 1 (D.f + P_i + Q_j + SiLU, S written split), both conditionings"),
+                        "achieved": fou_tflops, "peak": peak, "unit": "TFLOP/s",
+                        "frac": (fou_tflops / peak) if fou_tflops else None, "flops_per_launch": fou_flops,
+                        "avg_ms": ms_fou / nfou if nfou else None},
+        "path": {"tflops": step_flops / s_per_step / 1e12, "mfma_frac": step_flops / s_per_step / 1e12 / peak,
+                 "math": math, "flops_per_step_per_gpu": step_flops,
+                 "edge_fourier_avg_ms": ms_fou / nfou if nfou else None,
+                 "decoder_pair_avg_ms": ms_dec / ndec if ndec else None},
+        "noise_host_draw_ms": draw_ms,
+        "noise_host_draw_ms_8rank_share": draw_ms_8,
+        "edge_repairs": events["layer_repairs"] + events["tail_repairs"],
+        "edge_events": dict(events, note="device counters over warm-up, timed and eager passes (chm_prof_events): "
+                                         "repairs recompute a layer whose intra-grid check failed; 0 = none ran"),
+        "cpu_baseline": None,
+    }
+    if rank == 0 and world == 1 and not args.no_api_legs and not args.ragged:
+        try:
+            out["api"] = api_legs(model, total, args.n_atoms, cond, null, args.seed, value)
+        except Exception as e:  # noqa: BLE001
+            out["api"] = {"error": repr(e)}
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        try:
+            out["cpu_baseline"] = cpu_baseline(args.cpu_samples, args.n_atoms, args.cpu_steps)
+        except Exception as e:  # noqa: BLE001
+            out["cpu_baseline"] = {"error": repr(e)}
+    return out
+
+
 def launch_plan(gpus, env, device_count):
     """What `bench.py --gpus N` does in this process, decided before anything touches the GPU.
 
@@ -461,7 +659,7 @@ def main():
 
     model.decoder.set_math(args.math)
     draw_ms = draw_ms_8 = None
-    if args.noise == "torch":
+    if args.noise == "torch" and args.full:
         # parity mode: every rank seeds the CPU generator alike and draws the whole job's tensors (initial
         # state and per-step noise), keeping its rows; the per-step host draw of this rank's share, timed alone
         from chemeleon_amd.noise import StepNoise
@@ -481,6 +679,7 @@ def main():
         for _ in range(10):
             sn8.draw(out=bufs8)
         draw_ms_8 = (time.perf_counter() - t0) / 10 * 1e3
+    if args.noise == "torch":
         torch.manual_seed(args.seed)
         it = model.sample_states(natoms, None, 2.0, 1e-5, noise="torch", text_embeds=cond, null_text_embeds=null,
                                  clone=False, node_base=node_base, graph_base=g0,
@@ -490,10 +689,11 @@ def main():
                                  null_text_embeds=null, clone=False, node_base=node_base, graph_base=g0, init=init,
                                  graph=not args.no_graph, lanes=args.lanes)
     next(it)  # initial state
-    _lib.prof_events(reset=True)  # edge-kernel health counters (wait timeouts, repairs) from here on
-    # per-kernel HIP-event instrumentation (eager launches only; graph captures are not instrumented)
-    _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
-    _lib.check(_lib.load().chm_prof_enable(1), "prof_enable")
+    if args.full:
+        _lib.prof_events(reset=True)  # edge-kernel health counters (wait timeouts, repairs) from here on
+        # per-kernel HIP-event instrumentation (eager launches only; graph captures are not instrumented)
+        _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
+        _lib.check(_lib.load().chm_prof_enable(1), "prof_enable")
     for _ in range(args.warmup):
         next(it)
     torch.cuda.synchronize()
@@ -507,108 +707,21 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if not args.no_graph:
-        # the timed steps replayed a captured graph: time the kernels with HIP events in an
-        # instrumented eager pass of 2 reverse steps on the same shapes, right after the timed region
-        _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
-        it2 = model.sample_states(natoms, None, 2.0, 1e-5, noise="philox", seed=args.seed, text_embeds=cond,
-                                  null_text_embeds=null, clone=False, node_base=node_base, graph_base=g0,
-                                  init=init, t_stop=998, graph=False)
-        for _ in it2:
-            pass
-        torch.cuda.synchronize()
-    # the dominant kernel: both edge layers in one grid (k_edge16_layer, the default on fc batches) or,
-    # when that is off, the edge message GEMM; with the one-grid kernel on, a second eager pass times the
-    # two layers as separate launches for context
-    nlay, ms_lay = _lib.prof_read(_lib.K_EDGE_LAYER)
-    ndec, ms_dec = _lib.prof_read(_lib.K_DECODER)
-    if nlay:
-        _lib.check(_lib.load().chm_prof_reset(), "prof_reset")
-        model.decoder.set_option("edge_layer", 0)
-        it3 = model.sample_states(natoms, None, 2.0, 1e-5, noise="philox", seed=args.seed, text_embeds=cond,
-                                  null_text_embeds=null, clone=False, node_base=node_base, graph_base=g0,
-                                  init=init, t_stop=998, graph=False)
-        for _ in it3:
-            pass
-        torch.cuda.synchronize()
-        model.decoder.set_option("edge_layer", 1)
-    _lib.check(_lib.load().chm_prof_enable(0), "prof_disable")
-    torch.cuda.synchronize()
-    events = _lib.prof_events()
     per_rank = [elapsed]
+    final = state[1:]  # what the caller iterating the path holds after the last timed step
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         every = [torch.zeros_like(tt) for _ in range(world)]
         dist.all_gather(every, tt)
         per_rank = [float(v.item()) for v in every]
         elapsed = max(per_rank)
-        ev = torch.tensor([events[k] for k in _lib.EVENT_NAMES], device=dev, dtype=torch.float64)
-        dist.all_reduce(ev)  # (summed over ranks)
-        events = {k: int(v) for k, v in zip(_lib.EVENT_NAMES, ev.tolist())}
         # finished structures -> every rank (the all-gather of the sampler; outside the timed region)
         from chemeleon_amd.distributed import gather_states
-        gather_states(state[1:], natoms, natoms_all=[all_nat[a:b] for a, b in ranges])
+        final = gather_states(state[1:], natoms, natoms_all=[all_nat[a:b] for a, b in ranges])[:3]
 
     s_per_step = elapsed / args.steps
     value = total / (s_per_step * T_STEPS)
-
-    # live per-kernel timing (HIP events on the launch stream)
-    nmsg, ms_msg = _lib.prof_read(_lib.K_EDGE_MESSAGE)
-    nfou, ms_fou = _lib.prof_read(_lib.K_EDGE_FOURIER)
-    E = sum(n * n for n in natoms)
-    N = sum(natoms)
-    msg_flops = 2.0 * (2 * E) * H * H  # one launch covers both conditionings
-    msg_tflops = msg_flops / (ms_msg / nmsg * 1e-3) / 1e12 if nmsg else None
-    seg_bytes = 2.0 * (E * H * 4 + N * H * 4)
-    step_flops = 2 * decoder_pair_flops(natoms)
     math = model.decoder.get_math()
-    Ep = sum(n * (n + 1) // 2 for n in natoms)
-    fou_flops = 2.0 * (Ep if edge_pairs_on() else E) * 768 * H  # edge layer 1: D.f once for both conditionings
-    # (on pairs: once per unordered pair, k_edge16_pairs)
-    fou_tflops = fou_flops / (ms_fou / nfou * 1e-3) / 1e12 if nfou else None
-    msg_kernel = ((pairs_layer_kernel() or "k_edge16_pairs") if edge_pairs_on() else "k_edge16_layer") if nlay \
-        else "k_edge16<2"
-    traffic, traffic_src = None, "not collected for the ragged workload" if args.ragged else "not collected"
-    if math == "split16" and not args.ragged:
-        if rank == 0 and world == 1 and not args.no_traffic:
-            try:
-                traffic, traffic_src = measure_traffic(args, msg_kernel)
-            except Exception as e:  # noqa: BLE001
-                traffic, traffic_src = None, {"error": repr(e)}
-        if traffic is None and (args.n_samples, args.n_atoms, world) == (512, 40, 1):  # (the stored profile's shape)
-            failed = traffic_src
-            traffic, traffic_src = _stored_traffic(msg_kernel)
-            if traffic_src is not None:
-                traffic_src["in_run"] = failed if not args.no_traffic and world == 1 else "skipped"
-    lay_flops = fou_flops + msg_flops
-    lay_tflops = lay_flops / (ms_lay / nlay * 1e-3) / 1e12 if nlay else None
-    # fp32-equivalent ceilings: bf16x3 = 2.5 PF / 6 products; split16 edge GEMMs = 2.5 PF (fp16 dense
-    # = bf16 rate) / 3 products; f32 = the fp32 MFMA peak
-    peak = {"bf16x3": BF16X3_PEAK_TFLOPS, "split16": MFMA_BF16_PEAK_TFLOPS / 3}.get(math, MFMA_F32_PEAK_TFLOPS)
-
-    # standalone message-passing aggregation kernel (chm_segment_mean) on the
-    # bench batch's edge layout, [2, E, 512] fp32 messages (HIP events)
-    seg_gbs = seg_ms = None
-    try:
-        b = model.decoder.hip_batch(natoms, 2)
-        msg = torch.empty(2, b.num_edges, H, device=dev).normal_()
-        agg = torch.empty(2, b.num_nodes, H, device=dev)
-        L_ = _lib.load()
-        st = _lib.stream_handle(dev)
-        for _ in range(2):
-            _lib.check(L_.chm_segment_mean(b.handle, 2, _lib.ptr(msg), msg.numel(), _lib.ptr(agg), agg.numel(), st), "segment_mean")
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            _lib.check(L_.chm_segment_mean(b.handle, 2, _lib.ptr(msg), msg.numel(), _lib.ptr(agg), agg.numel(), st), "segment_mean")
-        e1.record()
-        torch.cuda.synchronize()
-        seg_ms = e0.elapsed_time(e1) / 10
-        seg_gbs = seg_bytes / (seg_ms * 1e-3) / 1e9
-        del msg, agg
-    except Exception as e:  # noqa: BLE001
-        print("segment_mean microbench failed:", repr(e), file=sys.stderr)
-
     out = {
         "metric": ("structures/sec (1000-step sample, n_atoms=40)" if not args.ragged else
                    "structures/sec (1000-step sample, natoms = randint(1, 81), SURVEY C4)"),
@@ -639,77 +752,12 @@ def main():
                              f"rank {share_of[0]}'s share of a {share_of[1]}-rank job of {share_of[2]} crystals "
                              f"({total} crystals, {sum(all_nat)} atoms, {sum(n * n for n in all_nat)} edges), run alone "
                              "on one GPU; value counts this share's structures")},
-        "roofline": {"bound": "mfma",
-                     "timing": ("HIP events on the launch stream, eager pass of 2 steps after the timed graph replays"
-                                if not args.no_graph else "HIP events on the launch stream over warm-up + timed steps"),
-                     "kernel": {"split16": ((f"both edge layers of a CSP layer in one grid, layer 1 on "
-                                             f"unordered pairs ({msg_kernel}: D.f once per pair i <= j, both "
-                                             "directions' S = SiLU(U +- V + P + Q); S.W2^T + SiLU + fused "
-                                             "scatter_mean; 16x16x32 MFMA), both conditionings, incl. its two repair "
-                                             "launches (no-ops unless a check fails)") if edge_pairs_on() else
-                                            ("both edge layers of a CSP layer in one grid (k_edge16_layer: D.f + P_i + "
-                                             "Q_j + SiLU -> S, S.W2^T + SiLU + fused scatter_mean; 16x16x32 MFMA), "
-                                             "both conditionings, incl. its two repair launches (no-ops unless a "
-                                             "check fails)")) if nlay else
-                                           (f"edge message GEMM + fused scatter_mean ({msg_kernel}, EPI_SEGMEAN, "
-                                            "16x16x32 MFMA), both conditionings"),
-                                "bf16x3": "edge message GEMM + fused scatter_mean (k_gemm3_big<EPI_SEGMEAN>), "
-                                          "both conditionings",
-                                "f32": "edge message GEMM (k_gemm, S.W2^T + SiLU, both conditionings)"}[math],
-                     "achieved": lay_tflops if nlay else msg_tflops, "peak": peak, "unit": "TFLOP/s",
-                     "frac": ((lay_tflops if nlay else msg_tflops) / peak) if (lay_tflops or msg_tflops) else None,
-                     "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "mfma_busy": (traffic_src.get("mfma_busy") if isinstance(traffic_src, dict) else None),
-                     "mfma_busy_note": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), in-run PMC "
-                                       "pass over the same probe as traffic",
-                     "traffic_algorithmic": (edge_layer_bytes(natoms) if nlay else message_layer_bytes(natoms)),
-                     "peak_note": {"bf16x3": "fp32-equivalent flops; bf16 dense MFMA 2.5 PF / 6 products",
-                                   "split16": "fp32-equivalent flops (3 fp16 MFMA products each); fp16 dense MFMA "
-                                           "2.5 PF / 3 products",
-                                   "f32": "fp32 MFMA dense peak"}[math],
-                     "flops_per_launch": lay_flops if nlay else msg_flops, "launches": nlay or nmsg,
-                     "avg_ms": (ms_lay / nlay) if nlay else (ms_msg / nmsg if nmsg else None)},
-        "msgpass": {"bound": "hbm", "kernel": "k_segment_mean (standalone scatter_mean, chm_segment_mean)",
-                    "achieved": seg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": (seg_gbs / HBM_PEAK_GBS) if seg_gbs else None, "bytes_per_launch": seg_bytes,
-                    "avg_ms": seg_ms,
-                    "note": ("in the sampler the aggregation is fused into the message GEMM epilogue; this is the "
-                             "standalone kernel on the same [2,E,512] shape" if math != "f32" else
-                             "the kernel as launched by the sampler")},
-        "edge_layer2": {"kernel": "edge layer 2 alone (k_edge16<2>: S.W2^T + SiLU + fused scatter_mean), both "
-                                  "conditionings" + (" (second eager pass, two launches per layer)" if nlay else ""),
-                        "achieved": msg_tflops, "peak": peak, "unit": "TFLOP/s",
-                        "frac": (msg_tflops / peak) if msg_tflops else None, "flops_per_launch": msg_flops,
-                        "avg_ms": ms_msg / nmsg if nmsg else None},
-        "edge_layer1": {"kernel": ("edge layer 1 on unordered pairs (k_edge16_pairs: D.f once per pair i <= j, both "
-                                   "directions' S = SiLU(U +- V + P + Q) written split), both conditionings"
-                                   if edge_pairs_on() else
-                                   "edge layer 1 (D.f + P_i + Q_j + SiLU, S written split), both conditionings"),
-                        "achieved": fou_tflops, "peak": peak, "unit": "TFLOP/s",
-                        "frac": (fou_tflops / peak) if fou_tflops else None, "flops_per_launch": fou_flops,
-                        "avg_ms": ms_fou / nfou if nfou else None},
-        "path": {"tflops": step_flops / s_per_step / 1e12, "mfma_frac": step_flops / s_per_step / 1e12 / peak,
-                 "math": math, "flops_per_step_per_gpu": step_flops,
-                 "edge_fourier_avg_ms": ms_fou / nfou if nfou else None,
-                 "decoder_pair_avg_ms": ms_dec / ndec if ndec else None},
-        "noise_host_draw_ms": draw_ms,
-        "noise_host_draw_ms_8rank_share": draw_ms_8,
-        "edge_repairs": events["layer_repairs"] + events["tail_repairs"],
-        "edge_events": dict(events, note="device counters over warm-up, timed and eager passes (chm_prof_events): "
-                                         "repairs recompute a layer whose intra-grid check failed; 0 = none ran"),
-        "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_api_legs and not args.ragged:
-        try:
-            out["api"] = api_legs(model, total, args.n_atoms, cond, null, args.seed, value)
-        except Exception as e:  # noqa: BLE001
-            out["api"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_samples, args.n_atoms, args.cpu_steps)
-        except Exception as e:  # noqa: BLE001
-            out["cpu_baseline"] = {"error": repr(e)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final)
+    if args.full:
+        out.update(full_legs(args, model, dev, dist, rank, world, natoms, total, cond, null, node_base, g0, init,
+                             s_per_step, value, math, draw_ms, draw_ms_8))
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -12,7 +12,7 @@ mkdir -p $O
 for r in $(seq 1 $R); do
   for i in "${!ARMS[@]}"; do
     f=$O/arm${i}_r${r}.json
-    env ${ARMS[$i]} timeout -k 10 300 python bench.py --no-api-legs --no-cpu-baseline --no-traffic --warmup 3 "$@" \
+    env ${ARMS[$i]} timeout -k 10 300 python bench.py --full --no-api-legs --no-cpu-baseline --no-traffic --warmup 3 "$@" \
       > $f 2> $f.err || { tail -n 20 $f.err; exit 1; }
     echo "[${ARMS[$i]}] $(python tools/bench_summary.py $f | head -1)"
   done

@@ -11,11 +11,11 @@ if [ -z "$NO_TESTS" ]; then
 fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
 tail -n 1 $O/smoke.txt
-timeout -k 10 420 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 420 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python tools/bench_summary.py $O/bench_default.json | head -3
 cd /tmp && export TMPDIR=/tmp
 for cfg in "512 40" "64 40" "64 20"; do
   set -- $cfg
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/p$1x$2 -o run --output-format csv -- python3 $R/bench.py --n-samples $1 --n-atoms $2 --steps 5 --warmup 2 --no-cpu-baseline --no-api-legs --no-traffic > $O/bench_$1x$2.json 2> $O/bench_$1x$2.err
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/p$1x$2 -o run --output-format csv -- python3 $R/bench.py --full --n-samples $1 --n-atoms $2 --steps 5 --warmup 2 --no-cpu-baseline --no-api-legs --no-traffic > $O/bench_$1x$2.json 2> $O/bench_$1x$2.err
   python $R/tools/bench_summary.py $O/bench_$1x$2.json | head -1
 done

@@ -4,6 +4,7 @@
 # fault, abort or timeout). Outputs go to gpurun_out/<tag>/.
 set -o pipefail
 TAG=$1; shift
+R=$PWD
 O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
@@ -22,21 +23,21 @@ for step in "$@"; do
       tail -n 3 $O/gputests.txt ;;
     bench)
       f=$O/bench_$(echo "$arg" | tr -c 'a-zA-Z0-9' '_' | cut -c1-60).json
-      timeout -k 10 600 python -u bench.py $arg > $f 2> $f.err || { tail -n 30 $f.err; exit 1; }
+      timeout -k 10 600 python -u bench.py --full $arg > $f 2> $f.err || { tail -n 30 $f.err; exit 1; }
       python tools/bench_summary.py $f ;;
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -n 20 $O/smoke.txt; exit 1; }
       tail -n 1 $O/smoke.txt ;;
     dist2)
       f=$O/dist2.json
-      CHM_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --n-samples 64 --steps 2 --warmup 1 \
+      CHM_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 2 --n-samples 64 --steps 2 --warmup 1 \
         --no-cpu-baseline $arg > $f 2> $f.err || { tail -n 30 $f.err; exit 1; }
       python tools/bench_summary.py $f ;;
     prof)
       D=$PWD/$O/prof_$(echo "$arg" | tr -c 'a-zA-Z0-9' '_' | cut -c1-60)
       mkdir -p $D
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $D -o run --output-format csv -- \
-        python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs --no-traffic $arg \
+        python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs --no-traffic $arg \
         > $D/bench.log 2>&1) || { tail -n 30 $D/bench.log; exit 1; }
       find $D -name '*kernel_stats.csv' -exec head -n 12 {} \; ;;
     *) echo "unknown step $step"; exit 2 ;;

@@ -9,7 +9,7 @@ tail -n 3 $O/tests.txt
 for NA in "512 40" "64 40"; do
   set -- $NA
   CHM_LIB=abl/trace/libchemeleon_hip.so CHM_EDGE_TRACE=$O/grid_${1}x${2}.bin CHM_EDGE_TRACE_LAYER=4 \
-    timeout -k 10 300 python bench.py --n-samples $1 --n-atoms $2 --steps 3 --warmup 1 --no-api-legs \
+    timeout -k 10 300 python bench.py --full --n-samples $1 --n-atoms $2 --steps 3 --warmup 1 --no-api-legs \
     --no-cpu-baseline --no-traffic > $O/t_${1}x${2}.json 2> $O/t_${1}x${2}.err
   python tools/grid_trace.py $O/grid_${1}x${2}.bin "${1}x${2}" | tee -a $O/trace_summary.txt
 done

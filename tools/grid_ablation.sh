@@ -8,7 +8,7 @@ TAG=$1; shift
 O=gpurun_out/$TAG
 mkdir -p $O
 for d in ${GRID_DBG:-0 4 16 524288 4194304}; do
-  CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs \
+  CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs \
     --no-traffic "$@" > $O/grid_d$d.json 2> $O/grid_d$d.err || { tail -n 20 $O/grid_d$d.err; exit 1; }
   echo "dbg $d: $(python tools/bench_summary.py $O/grid_d$d.json | head -1)"
 done

@@ -6,7 +6,7 @@ mkdir -p $O
 for NA in "512 40" "64 40" "256 40"; do
   set -- $NA
   CHM_LIB=abl/trace/libchemeleon_hip.so CHM_EDGE_TRACE=$O/grid_${1}x${2}.bin CHM_EDGE_TRACE_LAYER=4 \
-    timeout -k 10 300 python bench.py --n-samples $1 --n-atoms $2 --steps 3 --warmup 1 --no-api-legs \
+    timeout -k 10 300 python bench.py --full --n-samples $1 --n-atoms $2 --steps 3 --warmup 1 --no-api-legs \
     --no-cpu-baseline --no-traffic > $O/b_${1}x${2}.json 2> $O/b_${1}x${2}.err
   python tools/grid_trace.py $O/grid_${1}x${2}.bin "${1}x${2}" | tee -a $O/summary.txt
 done

@@ -12,7 +12,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 for d in 0 32768 65536 98304; do
-  CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs --no-traffic "$@" \
+  CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs --no-traffic "$@" \
     > $O/bench_d$d.json 2> $O/bench_d$d.err || { tail -n 20 $O/bench_d$d.err; exit 1; }
   python tools/bench_summary.py $O/bench_d$d.json
 done

@@ -10,7 +10,7 @@ TAG=$1; shift
 O=gpurun_out/$TAG
 mkdir -p $O
 for d in ${PAIRS_DBG:-0 16 4 131072 262144 524288 2097152}; do
-  CHM_EDGE_PAIRS=1 CHM_EDGE_PAIRS_LAYER=0 CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs \
+  CHM_EDGE_PAIRS=1 CHM_EDGE_PAIRS_LAYER=0 CHM_EDGE_DBG=$d timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-api-legs \
     --no-traffic "$@" > $O/pairs_d$d.json 2> $O/pairs_d$d.err || { tail -n 20 $O/pairs_d$d.err; exit 1; }
   python tools/bench_summary.py $O/pairs_d$d.json
 done

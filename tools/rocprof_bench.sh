@@ -4,4 +4,4 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 D=$R/gpurun_out/${PROF_DIR:-prof}
 mkdir -p $D
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $D -o run --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $D/bench.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $D -o run --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $D/bench.log 2>&1

@@ -4,4 +4,4 @@ R=${GRAFT_REPO_ROOT:-.}
 O=$R/gpurun_out/share5
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p -o run --output-format csv -- python3 $R/bench.py --ragged --n-samples 2048 --share 8 --steps 5 --warmup 2 --no-cpu-baseline --no-api-legs --no-traffic > $O/bench_share8.json 2> $O/bench_share8.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/p -o run --output-format csv -- python3 $R/bench.py --full --ragged --n-samples 2048 --share 8 --steps 5 --warmup 2 --no-cpu-baseline --no-api-legs --no-traffic > $O/bench_share8.json 2> $O/bench_share8.err
