@@ -57,6 +57,18 @@ class chm_step_io(ctypes.Structure):
                 ("d_rand_x2", c_void_p), ("n_rand_x2", c_i64)]
 
 
+class chm_debug_gemm_args(ctypes.Structure):
+    """One GEMM kernel on caller operands (test hook chm_debug_gemm, include/chemeleon_hip.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("act", ctypes.c_int32), ("M", c_i64), ("N", ctypes.c_int32),
+                ("K", ctypes.c_int32), ("ksplit", ctypes.c_int32), ("chunk_scaled", ctypes.c_int32),
+                ("d_A", c_void_p), ("lda", c_i64), ("d_A2", c_void_p), ("lda2", c_i64), ("d_W", c_void_p),
+                ("d_bias", c_void_p), ("d_R", c_void_p), ("ldr", c_i64), ("d_gb", c_void_p), ("ldgb", c_i64),
+                ("d_row2g", c_void_p), ("gb_rowmod", c_i64), ("gb_cols", ctypes.c_int32),
+                ("tile_rows", ctypes.c_int32), ("tile_cols", ctypes.c_int32), ("blocks_per_cu", ctypes.c_int32),
+                ("d_amax", c_void_p), ("d_amax2", c_void_p), ("d_C", c_void_p), ("ldc", c_i64),
+                ("d_cmax", c_void_p)]
+
+
 def step_io(a, x, lat, cond=None, null=None, noise=None, node0: int = 0, graph0: int = 0, nodes: int = None,
             graphs: int = None):
     """chm_step_io over tensors: the state (a [N] int64, x [N,3], lat [B,3,3]), conditioning rows
@@ -114,6 +126,7 @@ SIGNATURES = {
     "chm_debug_philox": (c_int, [c_u64, c_int, c_int, c_i64, c_i64, c_int, c_void_p, c_void_p]),
     "chm_debug_d3pm_philox": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64,
                                       c_i64, c_void_p, c_void_p]),
+    "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
     "chm_debug_layer_jobs": (c_i64, [c_i64, c_int, c_int, ctypes.POINTER(c_i64), c_i64]),
     "chm_debug_layer_seq": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "chm_debug_pair_plan": (c_i64, [ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32),

@@ -12,11 +12,12 @@
 // S16 (split16 mode): W pre-split into fp16 hi/lo rows [N][K/16][hi 16 | lo 16] of W * 2^-e_n
 // (split_rows_h, per-row power-of-two scale wscale[n] = 2^e_n, undone in the epilogue), A split by
 // each wave into fp16 hi/lo (round to nearest), three fp16 MFMA products (a_lo w_hi + a_hi w_lo +
-// a_hi w_hi): half the MFMAs of bf16x3, ~3.5 VALU per A element. A row r is scaled by 2^-e_r
+// a_hi w_hi): half the MFMAs of bf16x3, ~3.5 VALU per A element. A row r is scaled by 2^(14 - e_r)
 // before its split, e_r the exponent of max |A[r, :]| (g.amax / g.amax2, written by the kernel
 // that produced A: embed, film_ln, the segment-mean epilogue, or this kernel's own epilogue via
-// g.cmax), so every scaled entry is below 1 whatever the activations' range (the lattice terms
-// grow ~10^4x over a 1000-step trajectory); 2^e_r is applied again in the epilogue.
+// g.cmax), so every scaled entry is below 2^14 whatever the activations' range (the lattice terms
+// grow ~10^4x over a 1000-step trajectory) and the fp16 lo parts keep fp32-level accuracy also under an
+// amax that is only an upper bound (up to ~2^12 x); 2^(e_r - 14) is applied again in the epilogue.
 //
 // 128x128 tiles, 256 threads (4 waves of 64x64, C^T accumulators as in gemm_bf16x3.hip),
 // K-tiles of 16, a 4-deep ring of 20 KB stages (4 K-tiles in flight), two blocks per CU; S16 uses
@@ -63,6 +64,7 @@ template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_wai
 #define CHM_NODE_ABL 0
 #endif
 constexpr bool kNAblBar = CHM_NODE_ABL & 1, kNAblLd = CHM_NODE_ABL & 2, kNAblSplit = CHM_NODE_ABL & 4;
+constexpr int kS16Up = 14;  // split16 A rows scaled by amax: the row maximum's exponent after scaling
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -316,6 +318,10 @@ __global__ __launch_bounds__(256, NB) void k_node_gemm(GemmArgs g) {
         if (g.amax2) m = fmaxf(m, g.amax2[ar]);
         int e = 0;
         if (m > 0.f) frexpf(m, &e);
+        // the row's maximum lands in [2^13, 2^14), the top of the fp16 range, not in [0.5, 1): the lo parts' floor
+        // (fp16's subnormal quantum, 2^-25 absolute) is then 2^-39 of the maximum, so an amax that overstates
+        // the maximum by up to ~2^12 still leaves fp32-level parts; the exponent is kept inside the float range
+        e = e - kS16Up < -126 ? -126 : e - kS16Up > 126 ? 126 : e - kS16Up;
         asc[i] = ldexpf(1.0f, -e);
         aun[i] = ldexpf(1.0f, e);
       }

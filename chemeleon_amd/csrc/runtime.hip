@@ -1804,6 +1804,160 @@ extern "C" int chm_debug_d3pm_philox(int N, int A, int T, const float* logits, c
   return CHM_OK;
 }
 
+// One GEMM kernel on caller operands (tests/test_gpu_gemm.py). Every argument check runs before the first HIP
+// call, so a refused call needs no device.
+extern "C" int chm_debug_gemm(const chm_debug_gemm_args* a, void* stream) {
+  if (!a) return fail(CHM_E_ARG, "args is NULL");
+  const int kind = a->kind;
+  auto bad = [&](const char* field, const std::string& why) {
+    return fail(CHM_E_ARG, std::string("chm_debug_gemm (kind ") + std::to_string(kind) + "): " + field + " " + why);
+  };
+  if (kind < 0 || kind > 5) return bad("kind", "must be in [0, 5]");
+  const bool node = kind == 3 || kind == 4, edge = kind == 5;
+  if (a->M < 1 || a->M > (1L << 24)) return bad("M", "must be in [1, 2^24]");
+  if (a->N < 1 || a->K < 1) return bad(a->N < 1 ? "N" : "K", "must be positive");
+  if (!a->d_A) return bad("d_A", "is NULL");
+  if (!a->d_W) return bad("d_W", "is NULL");
+  if (!a->d_C) return bad("d_C", "is NULL");
+  if (a->act != 0 && a->act != 1) return bad("act", "must be 0 or 1");
+  const int nmult = (kind == 2 || edge) ? 256 : 128;
+  if (a->N % nmult) return bad("N", "must be a multiple of " + std::to_string(nmult));
+  const int kmult = edge ? 64 : (kind == 0 || kind == 2) ? 16 : 32;
+  if (a->K % kmult) return bad("K", "must be a multiple of " + std::to_string(kmult));
+  int ksplit = a->ksplit;
+  if (!a->d_A2) {
+    if (ksplit != 0 && ksplit != a->K) return bad("ksplit", "must be 0 or K without d_A2");
+    ksplit = a->K;
+  } else {
+    if (edge) return bad("d_A2", "is not taken by the edge GEMM");
+    if (ksplit < 16 || ksplit >= a->K || ksplit % 16) return bad("ksplit", "must be a multiple of 16 in (0, K)");
+    if (a->lda2 < a->K - ksplit || a->lda2 % 4) return bad("lda2", "must be >= K - ksplit and a multiple of 4");
+  }
+  if (a->lda < ksplit || a->lda % 4) return bad("lda", "must cover the row and be a multiple of 4");
+  if (a->ldc < a->N || a->ldc % 4) return bad("ldc", "must be >= N and a multiple of 4");
+  if (a->d_R && (a->ldr < a->N || a->ldr % 4)) return bad("ldr", "must be >= N and a multiple of 4");
+  if (a->d_gb) {
+    if (kind == 2) return bad("d_gb", "is not taken by gemm_bf16x3_big");
+    if (!a->d_row2g) return bad("d_row2g", "is NULL");
+    if (a->gb_rowmod < 1) return bad("gb_rowmod", "must be >= 1");
+    if (a->gb_cols < 4 || a->gb_cols > a->N || a->gb_cols % 4) return bad("gb_cols", "must be a multiple of 4 in (0, N]");
+    if (a->ldgb < a->gb_cols || a->ldgb % 4) return bad("ldgb", "must be >= gb_cols and a multiple of 4");
+  }
+  if (edge && (a->d_bias || a->act || a->d_R || a->d_gb))
+    return bad(a->d_bias ? "d_bias" : a->act ? "act" : a->d_R ? "d_R" : "d_gb", "is not taken by the edge GEMM's plain epilogue");
+  if (a->chunk_scaled != 0 && a->chunk_scaled != 1) return bad("chunk_scaled", "must be 0 or 1");
+  if (a->chunk_scaled && !edge) return bad("chunk_scaled", "is an option of kind 5");
+  if (a->chunk_scaled && (a->K % 128 || a->K > 512)) return bad("chunk_scaled", "needs K % 128 == 0 and K <= 512");
+  if (a->d_cmax && kind != 4) return bad("d_cmax", "is written by kind 4 only");
+  const int tr = a->tile_rows, tc = a->tile_cols, nb = a->blocks_per_cu;
+  if (!node && (tr || tc || nb)) return bad(tr ? "tile_rows" : tc ? "tile_cols" : "blocks_per_cu", "is an option of kinds 3 and 4");
+  if (tr != 0 && tr != 64 && tr != 128) return bad("tile_rows", "must be 0, 64 or 128");
+  if (kind == 3) {
+    if (tc != 0 && tc != 128) return bad("tile_cols", "must be 0 or 128 (bf16x3 tiles have 128 columns)");
+    if (nb != 0 && nb != 2) return bad("blocks_per_cu", "must be 0 or 2 (bf16x3 tiles run two blocks per CU)");
+  } else if (kind == 4) {
+    if (tc != 0 && tc != 64 && tc != 128) return bad("tile_cols", "must be 0, 64 or 128");
+    if (tc == 64 && tr != 64) return bad("tile_cols", "64 needs tile_rows 64");
+    if (nb != 0 && (nb < 2 || nb > 4)) return bad("blocks_per_cu", "must be 0, 2, 3 or 4");
+    if (nb && !tr) return bad("blocks_per_cu", "needs tile_rows");
+    if (tr == 64 && tc == 64 && nb != 0 && nb != 4) return bad("blocks_per_cu", "must be 0 or 4 on 64x64 tiles");
+    if (tr == 64 && tc == 128 && nb == 2) return bad("blocks_per_cu", "must be 0, 3 or 4 on 64-row tiles");
+    if (tr == 64 && tc == 0 && nb) return bad("blocks_per_cu", "needs tile_cols on 64-row tiles");
+    if (tr == 128 && nb == 4) return bad("blocks_per_cu", "must be 0, 2 or 3 on 128-row tiles");
+  }
+  for (const void* p : {(const void*)a->d_A, (const void*)a->d_A2, (const void*)a->d_W, (const void*)a->d_bias,
+                        (const void*)a->d_R, (const void*)a->d_gb, (const void*)a->d_C})
+    if ((uintptr_t)p % 16) return bad("operands", "must be 16-byte aligned");
+
+  hipStream_t s = (hipStream_t)stream;
+  const long M = a->M;
+  const int N = a->N, K = a->K;
+  void* mem = nullptr;  // the packed weights (+ row scales), and kind 5's split A rows (+ chunk exponents)
+  const size_t wbytes = ((kind >= 1 && kind <= 3 ? (size_t)3 * N * K * 2 : kind >= 4 ? (size_t)N * K * 4 : 0) + 255) / 256 * 256;
+  const size_t scbytes = ((size_t)N * 4 + 255) / 256 * 256;
+  const size_t abytes = edge ? (size_t)(M + 256) * K * 4 : 0, ebytes = edge ? ((size_t)M * 4 + 255) / 256 * 256 : 0;
+  if (kind != 0) HIPCHK(hipMalloc(&mem, wbytes + scbytes + abytes + ebytes));
+  char* base = (char*)mem;
+  float* wsc = (float*)(base + wbytes);
+  char* As = base + wbytes + scbytes;
+  int* aexp = (int*)(As + abytes);
+  auto done = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (mem) (void)hipFree(mem);
+    return e == hipSuccess ? CHM_OK : fail(CHM_E_HIP, std::string("chm_debug_gemm: ") + what + ": " + hipGetErrorString(e));
+  };
+  hipError_t e = hipSuccess;
+  if (kind >= 1 && kind <= 3) e = split_planes(a->d_W, (long)N * K, base, s);
+  if (kind == 4) e = split_rows_h(a->d_W, N, K, base, wsc, 0, s, 16);
+  if (edge) e = split_rows_h(a->d_W, N, K, base, wsc, 0, s);
+  if (e != hipSuccess) return done(e, "weight packing");
+
+  if (edge) {
+    // A as split rows [K/32][hi 32 | lo 32] (edge16.hip): unscaled like the Fourier features, or per (row, 128-column
+    // chunk) scaled by 2^-e, e the exponent of the chunk's maximum, like S; 256 readable rows behind the last (NaN:
+    // the kernel reads them for a partial tile and must store nothing of them)
+    std::vector<float> hA((size_t)M * K);
+    e = hipMemcpy2DAsync(hA.data(), (size_t)K * 4, a->d_A, (size_t)a->lda * 4, (size_t)K * 4, M, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return done(e, "A download");
+    std::vector<uint16_t> hs((size_t)(M + 256) * K * 2, (uint16_t)0x7e00);
+    std::vector<int> he(M, 0);
+    for (long r = 0; r < M; ++r) {
+      const float* x = hA.data() + (size_t)r * K;
+      _Float16* o = reinterpret_cast<_Float16*>(hs.data()) + (size_t)r * 2 * K;
+      for (int c0 = 0; c0 < K; c0 += 128) {
+        const int cn = K - c0 < 128 ? K - c0 : 128;
+        int ex = 0;
+        if (a->chunk_scaled) {
+          float m = 0.f;
+          for (int k = c0; k < c0 + cn; ++k) m = fmaxf(m, fabsf(x[k]));
+          if (m > 0.f) frexpf(m, &ex);
+          ex = ex < -126 ? -126 : ex > 127 ? 127 : ex;
+          he[r] |= (ex & 0xff) << (8 * (c0 / 128));
+        }
+        const float sc = ldexpf(1.0f, -ex);
+        for (int k = c0; k < c0 + cn; ++k) {
+          const float v = x[k] * sc;
+          const _Float16 hi = (_Float16)v;
+          o[(k / 32) * 64 + k % 32] = hi;
+          o[(k / 32) * 64 + 32 + k % 32] = (_Float16)(v - (float)hi);
+        }
+      }
+    }
+    e = hipMemcpyAsync(As, hs.data(), abytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(aexp, he.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the host vectors go out of scope)
+    if (e != hipSuccess) return done(e, "A upload");
+    EdgeArgs g{};
+    g.M = M; g.N = N; g.K = K; g.A = As; g.aexp = a->chunk_scaled ? aexp : nullptr;
+    g.W = base; g.wscale = wsc; g.C = a->d_C; g.ldc = a->ldc;
+    return done(edge_gemm16(g, EPI_STD, s), "edge_gemm16");
+  }
+
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K;
+  g.A = a->d_A; g.lda = a->lda;
+  g.A2 = a->d_A2 ? a->d_A2 : a->d_A; g.lda2 = a->d_A2 ? a->lda2 : a->lda; g.ksplit = ksplit;
+  g.W = a->d_W; g.ldw = K;
+  g.C = a->d_C; g.ldc = a->ldc;
+  g.bias = a->d_bias; g.act = a->act;
+  g.R = a->d_R; g.ldr = a->ldr;
+  g.gb = a->d_gb; g.ldgb = a->ldgb; g.gb_cols = a->gb_cols; g.row2g = a->d_row2g; g.gb_rowmod = a->d_gb ? a->gb_rowmod : 1;
+  if (kind != 0) g.Wp3 = base;
+  if (kind == 4) {
+    g.wscale = wsc;
+    g.amax = a->d_amax; g.amax2 = a->d_amax ? a->d_amax2 : nullptr; g.cmax = a->d_cmax;
+  }
+  if (kind == 0) return done(gemm(g, EPI_STD, s), "gemm");
+  if (kind == 1) return done(gemm_bf16x3(g, EPI_STD, s), "gemm_bf16x3");
+  if (kind == 2) return done(gemm_bf16x3_big(g, EPI_STD, s), "gemm_bf16x3_big");
+  const int r0 = g_node_rows, c0 = g_node_cols, b0 = g_node_blocks;
+  g_node_rows = tr; g_node_cols = tc; g_node_blocks = nb;
+  e = node_gemm(g, s);
+  g_node_rows = r0; g_node_cols = c0; g_node_blocks = b0;
+  return done(e, "node_gemm");
+}
+
 extern "C" int chm_edge_features(chm_batch* b, const float* x, float* feat, void* stream) {
   if (!b || !x || !feat) return fail(CHM_E_ARG, "NULL argument");
   HIPCHK(fourier(x, b->ei, b->ej, b->E, feat, (hipStream_t)stream));

@@ -332,6 +332,42 @@ int chm_debug_d3pm_philox(int N, int A, int T, const float* d_logits, const int6
                           const float* d_q_one_step, const float* d_q_mats, uint64_t seed, int64_t node_base,
                           int64_t* d_out, void* stream);
 
+/* Test hook: one GEMM kernel of the decoder on caller-supplied fp32 device operands,
+ * C[M,N] = epi(A[M,K] . W[N,K]^T), the weights packed exactly as chm_model_create packs them
+ * (bf16 planes for kinds 1-3, row-scaled fp16 split rows in 16-column chunks for kind 4, in
+ * 32-column chunks for kind 5). For tests only: it allocates, and synchronises the stream.
+ *   kind 0 gemm (fp32 MFMA), 1 gemm_bf16x3, 2 gemm_bf16x3_big, 3 node_gemm bf16x3,
+ *   4 node_gemm split16, 5 edge_gemm16 with the plain epilogue (main loop + the W-scale undo).
+ *   d_A2 / lda2 / ksplit: columns k >= ksplit of A come from d_A2[:, k - ksplit] (NULL: none, and
+ *     ksplit is 0 or K). Epilogue: + d_bias[n]; + d_gb[d_row2g[row % gb_rowmod]][n] for n < gb_cols;
+ *     act 1 = SiLU; + d_R[row][n] (d_R may equal d_C). Kind 2 takes no gb; kind 5 no A2 and no epilogue.
+ *   d_amax / d_amax2 (kind 4 only, ignored elsewhere; NULL = unscaled): per row an upper bound of
+ *     max |A[row, :]| / max |A2[row, :]|, whose exponent sets the row's split scale.
+ *   d_cmax (kind 4 only; NULL = skip): [M] words the caller zero-fills; receives max |C[row, :]| as float bits.
+ *   tile_rows / tile_cols / blocks_per_cu (kinds 3, 4; 0 = the kernel's own choice): the node GEMM's tile
+ *     variant, 64 or 128 rows, 64 or 128 columns (64: kind 4 with 64 rows), 2-4 blocks per CU as the variant has.
+ *   chunk_scaled (kind 5): A is split per (row, 128-column chunk) scaled by the chunk's exponent, as edge
+ *     layer 1 writes S (K % 128 == 0, K <= 512); 0: A is split unscaled, as the Fourier features are (|a| <= 1).
+ * Every argument check runs before any HIP call: a shape or option the kind does not accept returns
+ * CHM_E_ARG with chm_last_error() naming the field, without a device. */
+typedef struct chm_debug_gemm_args {
+  int32_t kind, act;
+  int64_t M;
+  int32_t N, K, ksplit, chunk_scaled;
+  const float* d_A; int64_t lda;
+  const float* d_A2; int64_t lda2;
+  const float* d_W;                 /* [N][K] */
+  const float* d_bias;
+  const float* d_R; int64_t ldr;
+  const float* d_gb; int64_t ldgb;
+  const int32_t* d_row2g; int64_t gb_rowmod;
+  int32_t gb_cols, tile_rows, tile_cols, blocks_per_cu;
+  const float* d_amax; const float* d_amax2;
+  float* d_C; int64_t ldc;
+  uint32_t* d_cmax;
+} chm_debug_gemm_args;
+int chm_debug_gemm(const chm_debug_gemm_args* args, void* stream);
+
 /* Host-only test hook (no device): the row tiles edge layer 2 runs on for an fc batch of these
  * crystals (EdgeArgs::rtiles; DESIGN.md "Edge layer 2 on row tiles"). Returns the tile count R (or a
  * negative CHM_E_*); if out4 holds >= 4 R int32 it receives per tile {first node starting in the tile,
