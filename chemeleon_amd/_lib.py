@@ -167,6 +167,12 @@ SIGNATURES = {
     "chm_prof_read": (c_int, [c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "chm_prof_events": (c_int, [ctypes.POINTER(c_i64), c_int]),
     "chm_prof_events_reset": (c_int, []),
+    "chm_snapshot_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(ctypes.c_uint8), c_int,
+                                    ctypes.POINTER(c_void_p)]),
+    "chm_snapshot_destroy": (None, [c_void_p]),
+    "chm_snapshot_slot_bytes": (ctypes.c_size_t, [c_void_p]),
+    "chm_snapshot_run": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                 ctypes.c_size_t, c_void_p]),
     "chm_mt19937_uniform": (c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), c_i64, c_i64, c_i64, c_void_p]),
 }

@@ -43,6 +43,7 @@ import torch.nn as nn
 from chemeleon_amd import _lib
 from chemeleon_amd.config import default_config
 from chemeleon_amd.modules.cspnet import CSPNet, SinusoidalTimeEmbeddings
+from chemeleon_amd.modules import schema as _schema
 from chemeleon_amd.modules.schema import TrajectoryContainer, TrajectoryStep, step_to_atoms
 from chemeleon_amd.noise import StepNoise
 from chemeleon_amd.utils.diff_utils import D3PM, BetaScheduler, SigmaScheduler
@@ -537,11 +538,27 @@ class Chemeleon(nn.Module):
     @torch.no_grad()
     def _sample_generator(self, natoms: Union[int, List[int]], texts: Optional[Union[str, List[str]]] = None,
                           cond_scale: float = 2.0, step_lr: float = 1e-5, *, distributed: Optional[bool] = None,
-                          group=None, **kw):
+                          group=None, overlap: bool = True, **kw):
         """chemeleon.py:305-467: yields, for every step t -> t-1, the list of
         structures at t-1 (TrajectoryContainer.get_atoms, schema.py:57-83).
+
+        overlap=True (the default, single process): the conversion stays one step behind the sampler.
+        After each reverse step is enqueued, a device kernel packs its state in output order (clamped,
+        atoms sorted by symbol: chm_snapshot_run) into a slot of a small ring and a copy stream brings the
+        slot to pinned host memory (schema.StateStreamer); the generator then asks sample_states for the
+        NEXT step, which enqueues its replay, before it waits for the previous slot's copy, slices the
+        structures out of it and yields them. So the host-side conversion of step t runs while the device
+        computes the step after it, for fc and knn edges, graph and eager stepping and both noise modes.
+        The structures are exactly those of overlap=False. One visible difference: with noise="torch" a
+        consumer that abandons the generator early has advanced the global CPU generator by one more step's
+        draws than with overlap=False; exhausting the generator leaves it exactly where overlap=False does.
+
+        overlap=False: every step is converted by step_to_atoms (three blocking copies of the live state
+        and a per-structure sort on the host) before the next one is enqueued.
+
         Under torch.distributed (see sample) the crystals are sharded over
-        the ranks and every step's whole batch is all-gathered to every rank."""
+        the ranks and every step's whole batch is all-gathered to every rank; that path converts with the
+        blocking step_to_atoms whatever `overlap` says."""
         if isinstance(natoms, int):
             natoms = [natoms]
         if texts is not None and isinstance(texts, str):
@@ -550,15 +567,30 @@ class Chemeleon(nn.Module):
             from chemeleon_amd.distributed import sample_states_distributed
             it = sample_states_distributed(self, natoms, texts, cond_scale, step_lr, group=group, every_step=True,
                                            **kw)
+            overlap = False
         else:
             it = self.sample_states(natoms, texts, cond_scale, step_lr, clone=False, **kw)
         next(it)
-        for t, a, x, lat in it:
-            yield step_to_atoms(a, x, lat, natoms)
+        if not overlap:
+            for t, a, x, lat in it:
+                yield step_to_atoms(a, x, lat, natoms)
+            return
+        streamer = _schema.StateStreamer(natoms, self.device)
+        try:
+            pending = None
+            for t, a, x, lat in it:  # (the step that produces this state is enqueued, not waited for)
+                ticket = streamer.push(a, x, lat)
+                if pending is not None:
+                    yield streamer.pop(pending)
+                pending = ticket
+            if pending is not None:
+                yield streamer.pop(pending)
+        finally:
+            streamer.close()
 
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
-               group=None, **kw):
+               group=None, overlap: bool = True, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -573,14 +605,18 @@ class Chemeleon(nn.Module):
         returns the whole batch. In the default noise="torch" mode the result
         is bit-identical to the single-process call. Only the final state is
         exchanged, unless stream / return_trajectory ask for every step.
-        distributed=False keeps each rank's call local."""
+        distributed=False keeps each rank's call local.
+
+        stream / return_trajectory convert every step to structures; overlap=True (default) does that one
+        step behind the sampler from a device-side snapshot, overlap=False with the blocking step_to_atoms
+        (see _sample_generator). The results are identical."""
         natoms = [n_atoms] * n_samples
         texts = [text_input] * n_samples if text_input is not None else None
         kw.update(distributed=distributed, group=group)
         if stream:
-            return self._sample_generator(natoms, texts, cond_scale, step_lr, **kw)
+            return self._sample_generator(natoms, texts, cond_scale, step_lr, overlap=overlap, **kw)
         if return_trajectory:
-            return list(self._sample_generator(natoms, texts, cond_scale, step_lr, **kw))
+            return list(self._sample_generator(natoms, texts, cond_scale, step_lr, overlap=overlap, **kw))
         kw.pop("distributed"), kw.pop("group")
         if self._distributed(distributed, group):
             from chemeleon_amd.distributed import sample_states_distributed

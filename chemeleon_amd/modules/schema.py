@@ -143,6 +143,139 @@ def step_to_atoms(atom_types, frac_coords, lattices, num_atoms, idx: int = None)
 
 
 # ---------------------------------------------------------------------------------------------
+# Streaming output: the state snapshot made on the device (chm_snapshot_*, include/chemeleon_hip.h)
+# and the structures sliced out of it.
+# ---------------------------------------------------------------------------------------------
+def symbol_rank_table() -> np.ndarray:
+    """rank[z] = position of CHEMICAL_SYMBOLS[z] among the sorted symbols (uint8 [104]): the sort key
+    of the device snapshot, so that sorting by it is sorting by symbol as `sort_atoms` does."""
+    order = sorted(range(len(CHEMICAL_SYMBOLS)), key=lambda z: CHEMICAL_SYMBOLS[z])
+    rank = np.empty(len(CHEMICAL_SYMBOLS), dtype=np.uint8)
+    rank[order] = np.arange(len(CHEMICAL_SYMBOLS), dtype=np.uint8)
+    return rank
+
+
+def slot_layout(natoms) -> Dict[str, int]:
+    """Byte offsets of one packed snapshot slot (include/chemeleon_hip.h): lattices f32 [B*9], frac f32
+    [N*3] (sorted), perm i32 [N], numbers u8 [N] (sorted); `bytes` = the slot size, a multiple of 16."""
+    B, N = len(natoms), int(sum(natoms))
+    lay = {"lattices": 0, "frac": 36 * B, "perm": 36 * B + 12 * N, "numbers": 36 * B + 16 * N}
+    lay["bytes"] = (36 * B + 17 * N + 15) // 16 * 16
+    return lay
+
+
+def slot_to_atoms(slot, natoms) -> List:
+    """The structures of one packed host slot (a uint8 buffer of `slot_layout(natoms)["bytes"]` bytes: a
+    numpy array, a CPU torch tensor or anything with the buffer protocol): what `step_to_atoms` returns for
+    the state the slot was made from. The atoms are already clamped and sorted, so each structure is a
+    slice; every array is copied out of the slot (astype), which its owner reuses for a later step."""
+    if torch.is_tensor(slot):
+        slot = slot.numpy()
+    buf = np.frombuffer(slot, dtype=np.uint8)
+    nat = [int(n) for n in (natoms.tolist() if torch.is_tensor(natoms) else natoms)]
+    B, N = len(nat), sum(nat)
+    lay = slot_layout(nat)
+    if buf.size != lay["bytes"]:
+        raise ValueError(f"slot of {buf.size} bytes, these crystals need {lay['bytes']}")
+    lat = buf[:lay["frac"]].view(np.float32).reshape(B, 3, 3)
+    x = buf[lay["frac"]:lay["perm"]].view(np.float32).reshape(N, 3)
+    num = buf[lay["numbers"]:lay["numbers"] + N]
+    out, off = [], 0
+    for g, n in enumerate(nat):
+        out.append(make_atoms(num[off:off + n].astype(np.int64), lat[g].astype(np.float64),
+                              x[off:off + n].astype(np.float64)))
+        off += n
+    return out
+
+
+class StateStreamer:
+    """Hands sampler states to the host as structure lists without stalling the sampler.
+
+    A ring of `slots` (>= 2) device slots with matching pinned host slots, a copy stream and per-slot
+    events. `push(a, x, lat)` enqueues the snapshot kernel on the CURRENT stream (so, called between two
+    replays of the reverse step, it reads the state the first one produced), then the slot's copy to
+    pinned memory on the copy stream behind an event; before a device slot is written again the compute
+    stream waits, on the device, for the copy that last read it. `pop(ticket)` blocks the host on that
+    slot's copy event only and returns `slot_to_atoms` of it (copied out: the slot is reused). A slot
+    pushed again before it was popped is an error."""
+
+    def __init__(self, natoms, device, slots: int = 2):
+        from chemeleon_amd import _lib
+        import ctypes
+        if slots < 2:
+            raise ValueError("StateStreamer needs a ring of at least 2 slots")
+        self._lib = _lib
+        self.natoms = [int(n) for n in natoms]
+        self.device = torch.device(device)
+        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
+        rank = symbol_rank_table()
+        plan = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().chm_snapshot_create(
+                nat, len(self.natoms), rank.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(rank),
+                ctypes.byref(plan)), "chm_snapshot_create")
+        self._plan = plan
+        self.slot_bytes = int(_lib.load().chm_snapshot_slot_bytes(plan))
+        assert self.slot_bytes == slot_layout(self.natoms)["bytes"]
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self._dev = [torch.empty(self.slot_bytes, dtype=torch.uint8, device=self.device) for _ in range(slots)]
+        for d in self._dev:  # (read on the copy stream: the allocator must not hand the block on before that)
+            d.record_stream(self.copy_stream)
+        self._pin = [torch.empty(self.slot_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+        self._snapped = [torch.cuda.Event() for _ in range(slots)]
+        self._copied = [torch.cuda.Event() for _ in range(slots)]
+        self._busy = [False] * slots      # pushed, not yet popped
+        self._used = [False] * slots      # _copied[k] has been recorded
+        self.uses = [0] * slots           # pushes per slot
+        self._head = 0
+
+    def push(self, atom_types, frac_coords, lattices) -> int:
+        """Snapshot of this state into the next slot; returns the ticket for `pop`. No host wait."""
+        L = self._lib
+        k = self._head % len(self._dev)
+        if self._busy[k]:
+            raise RuntimeError("StateStreamer: every slot of the ring holds a state that was not popped")
+        L.require_device(atom_types, frac_coords, lattices)
+        cur = torch.cuda.current_stream(self.device)
+        if self._used[k]:
+            cur.wait_event(self._copied[k])
+        L.check(L.load().chm_snapshot_run(
+            self._plan, L.ptr(atom_types), atom_types.numel(), L.ptr(frac_coords), frac_coords.numel(),
+            L.ptr(lattices), lattices.numel(), L.ptr(self._dev[k]), self.slot_bytes,
+            L.c_void_p(cur.cuda_stream)), "chm_snapshot_run")
+        self._snapped[k].record(cur)
+        self.copy_stream.wait_event(self._snapped[k])
+        with torch.cuda.stream(self.copy_stream):
+            self._pin[k].copy_(self._dev[k], non_blocking=True)
+        self._copied[k].record(self.copy_stream)
+        self._busy[k], self._used[k] = True, True
+        self.uses[k] += 1
+        self._head += 1
+        return k
+
+    def pop(self, ticket: int) -> List:
+        """The structures of the state pushed as `ticket`; blocks the host until that slot's copy is done."""
+        if not self._busy[ticket]:
+            raise RuntimeError("StateStreamer: this slot holds no pushed state")
+        self._copied[ticket].synchronize()
+        out = slot_to_atoms(self._pin[ticket].numpy(), self.natoms)
+        self._busy[ticket] = False
+        return out
+
+    def close(self):
+        if self._plan is not None:
+            self.copy_stream.synchronize()
+            self._lib.load().chm_snapshot_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+
+# ---------------------------------------------------------------------------------------------
 # CIF output (the reference's scripts convert the sampled ase.Atoms with pymatgen's
 # AseAtomsAdaptor and write `gen_{i}.cif`, chemeleon/scripts/sample_prompt.py:38-42; neither
 # pymatgen nor ase is needed here): P1 cell + fractional coordinates + symbols.

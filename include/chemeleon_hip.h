@@ -470,6 +470,37 @@ int chm_prof_events_reset(void);
 int chm_mt19937_uniform(uint32_t* state, int32_t* left, int32_t* next, int64_t count, int64_t lo, int64_t hi,
                         float* out);
 
+/* Snapshot of the sampler state in output order: what schema.step_to_atoms (the reference's
+ * TrajectoryContainer.get_atoms, schema.py:57-83) builds per crystal, made on the device so that streaming
+ * output copies one packed buffer per step and the host builds the structures by slicing.
+ *   numbers: classes outside [0, 103] become 0 (the reference clamps classes above 103; negative classes,
+ *     which the sampler never produces and the host path would index from the end of the symbol table, also
+ *     become 0);
+ *   order: within each crystal the atoms stand in STABLE order of chemical symbol (ase.build.tools.sort).
+ *     The key is h_rank[number], a table of n_rank = 104 entries < 104 that the caller derives from its
+ *     symbol table (string order, not atomic-number order: H < He, C < Ca < Cl; class 0 is X).
+ * The plan holds the crystals' node offsets and the rank table on the current device; it is independent of
+ * chm_model / chm_batch, so it also serves a batch gathered from several ranks. Any natoms >= 1 per crystal;
+ * more than 2^31 - 1 atoms in all return CHM_E_UNSUPPORTED. Bad arguments (NULL pointers, n_rank != 104,
+ * num_graphs <= 0, a natoms entry <= 0) return CHM_E_ARG before the device is touched.
+ * Slot layout (N atoms, B crystals; byte offsets):
+ *   0            lattices f32 [B*9]
+ *   36 B         frac     f32 [N*3], sorted
+ *   36 B + 12 N  perm     i32 [N]: the source atom's index inside its crystal, per sorted row
+ *   36 B + 16 N  numbers  u8  [N], sorted
+ * and the slot's size is 36 B + 17 N rounded up to a multiple of 16 bytes: the plan's slot_bytes (0 for a
+ * NULL plan). The run takes every buffer with its element count (the slot with its byte count, which must
+ * equal slot_bytes, at a 16-byte aligned address); a mismatch returns CHM_E_ARG naming the buffer and nothing
+ * is enqueued. It allocates nothing and does not synchronise: legal under stream capture. */
+typedef struct chm_snapshot chm_snapshot;
+int chm_snapshot_create(const int32_t* h_natoms, int num_graphs, const uint8_t* h_rank, int n_rank,
+                        chm_snapshot** out);
+void chm_snapshot_destroy(chm_snapshot* plan);
+size_t chm_snapshot_slot_bytes(const chm_snapshot* plan);
+int chm_snapshot_run(const chm_snapshot* plan, const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                     int64_t n_frac, const float* d_lattices, int64_t n_lattices, void* d_slot, size_t slot_bytes,
+                     void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
