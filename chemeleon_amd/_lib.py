@@ -127,6 +127,8 @@ SIGNATURES = {
     "chm_debug_d3pm_philox": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64,
                                       c_i64, c_void_p, c_void_p]),
     "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
+    "chm_debug_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                     c_void_p, c_void_p, c_void_p]),
     "chm_debug_layer_jobs": (c_i64, [c_i64, c_int, c_int, ctypes.POINTER(c_i64), c_i64]),
     "chm_debug_layer_seq": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "chm_debug_pair_plan": (c_i64, [ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32),

@@ -1345,6 +1345,228 @@ static int knn_build(chm_batch* b, const float* x, const float* lat, hipStream_t
   return CHM_OK;
 }
 
+// The schedule the edge layers of a decoder call with P conditionings take, from the model's options and the
+// batch's tables (run_decoder and chm_debug_edge_layer decide it here, once per call).
+struct EdgePlan {
+  bool n16;        // split16 node GEMMs: row maxima of their A operands, written by the producing kernels
+  bool ps;         // pre-split node GEMMs: the producers write the A operands split (no row-max atomics then)
+  bool pairs;      // fc edge layer 1 on unordered pairs (option edge_pairs): F holds the pairs' features only
+  bool pair_grid;  // both edge layers on pairs in one grid (k_edge16_pairs_grid) for this call
+  bool waits;      // a schedule with intra-grid waits: its flag words start clear in every call
+  bool zero_grid;  // the pair grid's repair requests and per-layer flags: zeroed by the embedding launch
+};
+static EdgePlan edge_plan(const chm_batch* b, int P) {
+  const chm_model* m = b->m;
+  EdgePlan p;
+  p.n16 = b->math == MATH_SPLIT16 && m->node16 && m->node_glds;
+  p.ps = p.n16 && m->node_ps && b->Hs;
+  p.pairs = b->math == MATH_SPLIT16 && m->edge_pairs && b->pe && !b->knn && b->E > 0;
+  // (edge layer 1 on pairs as two launches, the default below 256 row tiles: no intra-grid waits, nothing to clear;
+  // the memsets cost 4.8 us each per call, 0.9% of a 64x20 step)
+  p.pair_grid = p.pairs && m->edge_pairs_layer && m->edge_rows && b->rtiles && m->edge_layer && b->psched &&
+                P == b->P && b->nrt >= m->edge_layer_min && m->ncu > 0 && m->xcd_mask == 0xffu && b->rt_nbig < 0;
+  p.waits = !p.pairs || p.pair_grid;
+  p.zero_grid = b->xbad && b->math == MATH_SPLIT16 && p.pair_grid;
+  return p;
+}
+
+// k_edge16_layer / k_edge16_tail: repair requests (layer l: xbad[l], tail of layer l: xbad[kMaxLayers + l])
+// and row-tile flags start clear in every call (the flags also return to 0 at the end of every
+// launch; this keeps a timed-out wait from leaking into later calls). The pair grid's words (zero_grid) are
+// cleared by run_decoder's embedding launch; grid_too: here as well (chm_debug_edge_layer has no such launch).
+static int clear_edge_flags(chm_batch* b, const EdgePlan& ep, hipStream_t s, bool grid_too) {
+  const chm_model* m = b->m;
+  const int L = m->d.num_layers;
+  if (b->xbad && b->math == MATH_SPLIT16 && ep.waits && !ep.pair_grid) {
+    HIPCHK(hipMemsetAsync(b->xbad, 0, 2 * kMaxLayers * sizeof(unsigned), s));
+    if (!ep.pairs && m->edge_rows && m->edge_layer && m->edge_dyn && b->sched)
+      HIPCHK(hipMemsetAsync(b->sched, 0, (size_t)L * (16 + 8 * b->sched_cap) * sizeof(unsigned), s));
+    if (!ep.pairs && m->edge_rows && m->edge_layer) HIPCHK(hipMemsetAsync(b->lflags, 0, b->nrt * sizeof(unsigned), s));
+  }
+  if (grid_too && ep.zero_grid) {
+    HIPCHK(hipMemsetAsync(b->xbad, 0, 2 * kMaxLayers * sizeof(unsigned), s));
+    HIPCHK(hipMemsetAsync(b->psched, 0, (size_t)L * 8 * b->pplan.npx * sizeof(unsigned), s));
+  }
+  return CHM_OK;
+}
+
+// The Fourier features of the call's edges (pairs: of the (i, j) edges, i <= j) into F, in the math mode's form.
+static int edge_features(chm_batch* b, const EdgePlan& ep, const float* x, hipStream_t s) {
+  const long E = b->E;
+  const bool pairs = ep.pairs;
+  if (pairs)
+    HIPCHK(fourier_h(x, b->pi, b->pj, b->Ep, b->F, s, nullptr));  // (the (i, j) edges' features, i <= j)
+  else if (b->math == MATH_SPLIT16)
+    HIPCHK(fourier_h(x, b->ei, b->ej, E, b->F, s, b->knn ? b->fd : nullptr));  // fp16 hi/lo split rows
+  else
+    HIPCHK(fourier(x, b->ei, b->ej, E, b->F, s));
+  return CHM_OK;
+}
+
+// The message path of CSP layer l on the batch's buffers, every math mode: F (features) and PQ (the per-node halves
+// of edge layer 1, P with b1 + the per-graph term) -> agg = mean_j SiLU(SiLU(D f_ij + P[i] + Q[j]) W2^T + b2).
+// ps: agg is written as split rows + chunk exponents (aggs / agge) instead of fp32 rows + row maxima.
+static int edge_block(chm_batch* b, int P, int l, const EdgePlan& ep, bool ps, hipStream_t s) {
+  const chm_model* m = b->m;
+  const long N = b->N, E = b->E;
+  const LayerW& w = m->layers[l];
+  const bool pairs = ep.pairs, pair_grid = ep.pair_grid;
+  const long RS = (long)b->P * N;
+  auto rmx = [&](int k) { return ep.n16 && !ps ? b->rmx + k * RS : nullptr; };
+  if (b->math == MATH_SPLIT16 && E == 0) {  // (knn: no atom within any other's radius: every mean is 0)
+    HIPCHK(hipMemsetAsync(b->agg, 0, (size_t)P * N * H * sizeof(float), s));
+    if (ps) {
+      HIPCHK(hipMemsetAsync(b->aggs, 0, (size_t)P * N * H * 4, s));
+      HIPCHK(hipMemsetAsync(b->agge, 0, (size_t)P * N * sizeof(int), s));
+    }
+  } else if (b->math == MATH_SPLIT16) {
+    // split16: fp16 hi/lo split rows throughout (edge16.hip). S lives in S's bytes as
+    // split rows [P*E][H/32][2][32] plus one packed exponent word per row (rowmax buffer).
+    int* sexp = reinterpret_cast<int*>(b->rowmax);
+    // edge layer 1: S_c = SiLU(D f_ij + P_c[i] + Q_c[j]), D f shared by the pair
+    EdgeArgs e1;
+    std::memset(&e1, 0, sizeof(e1));
+    e1.M = E; e1.N = H; e1.K = FD; e1.A = b->F; e1.W = w.D2h; e1.wscale = w.Dsc;
+    e1.ei = b->ei; e1.ej = b->ej; e1.PQ = b->PQ; e1.nnodes = N; e1.npairs = P; e1.E = E;
+    e1.node_off = b->node_off; e1.natoms = b->natoms; e1.n2g = b->n2g;
+    e1.S = b->S; e1.sexp = sexp; e1.dbg = m->edge_dbg; e1.stagger = m->edge_stagger;
+    // edge layer 2 fused with the aggregation: agg = mean_j SiLU(S W2^T + b2)
+    EdgeArgs e2;
+    std::memset(&e2, 0, sizeof(e2));
+    e2.M = (long)P * E; e2.N = H; e2.K = H; e2.A = b->S; e2.aexp = sexp;
+    e2.W = w.W22h16; e2.wscale = w.W2sc; e2.bias = w.b2; e2.tiles = b->tiles;
+    e2.ntiles = b->ntiles;
+    e2.node_estart = b->node_estart; e2.natoms = b->natoms; e2.n2g = b->n2g; e2.agg = b->agg;
+    e2.node_n = b->node_n; e2.agg_max = reinterpret_cast<unsigned*>(rmx(RMX_AGG));
+    if (ps) { e2.aggs = b->aggs; e2.agge = b->agge; }
+    e2.nnodes = N; e2.npairs = P; e2.E = E; e2.dbg = m->edge_dbg; e2.stagger = m->edge_stagger;
+    if (m->edge_rows && b->rtiles) {  // 256-row tiles, cut nodes continued across tiles
+      e2.rtiles = b->rtiles; e2.ntiles = (int)b->nrt; e2.sbuf = b->sbuf; e2.msgbuf = b->msgbuf;
+      e2.rinfo = b->rinfo; e2.rinfo_n = b->rinfo_n;
+      e2.rcnt = b->rcnt; e2.r2tot = b->r2tot;
+    }
+    // edge layer 2 on the two-launch schedule: one launch, or on a mixed row tiling (short_row_tiles) its 256-row
+    // tiles, then its 192-row tiles (k_edge16_short)
+    auto layer2 = [&](const EdgeArgs& ga) -> hipError_t {
+      if (!ga.rtiles || b->rt_nbig < 0) return edge_gemm16(ga, EPI_SEGMEAN, s);
+      if (b->rt_nbig > 0) {
+        EdgeArgs gb = ga;
+        gb.rt_count = (int)b->rt_nbig;
+        if (hipError_t r = edge_gemm16(gb, EPI_SEGMEAN, s); r != hipSuccess) return r;
+      }
+      EdgeArgs gs = ga;
+      gs.rt_first = (int)b->rt_nbig;
+      gs.rt_count = (int)(b->nrt - b->rt_nbig);
+      gs.rt_h = kShortRows;
+      gs.rt_e0 = b->rt_nbig * kTileRows;
+      return edge_gemm16(gs, EPI_SEGMEAN, s);
+    };
+    // (instrumented eager launches keep one launch per layer, so the per-kernel timings stay whole;
+    // captured launches are never instrumented)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool instrumented = g_prof_on && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+    // (same-box A/B, static grid against two launches: 64x40 8.47 -> 7.77 ms per step, 512x40 54.9 -> 54.8,
+    // 64x20 2.95 -> 3.10: 100 row tiles leave each XCD's job list too short to pack; profiles/r5/grid/)
+    if (pair_grid) {
+      // both edge layers in one grid, layer 1 on pairs (k_edge16_pairs_grid)
+      EdgeArgs e1p = e1;
+      e1p.M = b->Ep; e1p.Mp = b->Ep; e1p.pi = b->pi; e1p.pj = b->pj; e1p.pe = b->pe; e1p.pnode = b->pnode;
+      e1p.xbad = e2.xbad = b->xbad + l;
+      PairSched ps;
+      ps.jobs = b->pjobs; ps.jstride = b->pplan.jstride;
+      ps.npx = b->pplan.npx; ps.pflag = b->psched + (size_t)l * 8 * b->pplan.npx; ps.R = b->nrt;
+      ProfScope ps_(CHM_K_EDGE_LAYER, s);
+      // (CHM_EDGE_TRACE_LAYER=4: block timelines of this grid, slot = blockIdx)
+      HIPCHK(traced_edge_launch(m, e2, 4, E, s, [&] {
+        ps.trace = e2.trace;
+        e2.trace = nullptr;
+        const hipError_t r = edge_gemm16_pairs_layer(e1p, e2, ps, m->repair_grid, s);
+        ps.trace = nullptr;
+        return r;
+      }));
+    } else if (pairs) {
+      // edge layer 1 on pairs (both directions' S rows per pair), then edge layer 2 on its row tiles
+      EdgeArgs e1p = e1;
+      e1p.M = b->Ep; e1p.Mp = b->Ep; e1p.pi = b->pi; e1p.pj = b->pj; e1p.pe = b->pe; e1p.pnode = b->pnode;
+      {
+        ProfScope ps(CHM_K_EDGE_FOURIER, s);
+        HIPCHK(edge_gemm16_pairs(e1p, s));
+      }
+      ProfScope ps(CHM_K_EDGE_MESSAGE, s);
+      HIPCHK(layer2(e2));
+    } else if (e2.rtiles && m->edge_layer && b->nrt >= m->edge_layer_min && b->rt_nbig < 0 &&
+               (!m->edge_trace || m->edge_trace_layer == 3)) {
+      // both layers in one grid: layer 2's row tiles behind layer 1's (k_edge16_layer)
+      e1.lflags = e2.lflags = b->lflags;
+      e1.xbad = e2.xbad = b->xbad + l;
+      ProfScope ps(CHM_K_EDGE_LAYER, s);
+      // (CHM_EDGE_TRACE_LAYER=3: block timelines of this grid, slot = blockIdx)
+      HIPCHK(traced_edge_launch(m, e1, 3, E, s, [&] {
+        e2.trace = e1.trace;
+        const hipError_t r =
+            m->ncu > 0 && m->xcd_mask == 0xffu &&
+                    (m->edge_dyn == 2 || (m->edge_dyn == 1 && b->nrt >= kDynMinTiles))
+                ? edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s,
+                                    b->sched + (size_t)l * (16 + 8 * b->sched_cap), (int)b->sched_cap, m->ncu,
+                                    m->edge_pool, m->edge_skip_xcd)
+                : edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s);
+        e2.trace = nullptr;
+        return r;
+      }));
+    } else if (b->l1_rows_a > 0 && b->xbad && m->edge_split && !instrumented && !m->edge_trace) {
+      // Edge layer 1 in whole rounds of the grid (rows [0, l1_rows_a)), then one grid with its
+      // partial last round first and all of edge layer 2's segment tiles behind it (the few that
+      // read those rows wait for them inside the grid). Same tiles, same arithmetic: bit-identical
+      // to one launch per layer.
+      EdgeArgs e1b = e1;
+      e1.M = b->l1_rows_a;
+      e1.zero_flags = b->tail_flags;
+      e1.nzero = (int)((E - b->l1_rows_a + kTileRows - 1) / kTileRows);
+      e1b.row_base = b->l1_rows_a;
+      e1b.flags = e2.flags = b->tail_flags;
+      e1b.flag_row0 = e2.flag_row0 = b->l1_rows_a;
+      e2.xbad = b->xbad + kMaxLayers + l;  // (a timed-out wait: the repair launches recompute edge layer 2)
+      HIPCHK(edge_gemm16(e1, EPI_EDGE, s));
+      HIPCHK(edge_gemm16_tail(e1b, e2, m->repair_grid, s));
+    } else {
+      {
+        ProfScope ps(CHM_K_EDGE_FOURIER, s);
+        HIPCHK(traced_edge_launch(m, e1, 1, E, s, [&] {
+          return edge_gemm16(e1, EPI_EDGE, s);
+        }));
+      }
+      ProfScope ps(CHM_K_EDGE_MESSAGE, s);
+      HIPCHK(traced_edge_launch(m, e2, 2, E, s, [&] {
+        return layer2(e2);
+      }));
+    }
+  } else {
+    {  // edge layer 1: S_c = SiLU(D f_ij + P_c[i] + Q_c[j]), D f shared by the pair
+      GemmArgs g = gargs(E, H, FD, b->F, FD, w.D, b->S, H);
+      g.ei = b->ei; g.ej = b->ej; g.PQ = b->PQ; g.nnodes = N; g.npairs = P; g.E = E;
+      ProfScope ps(CHM_K_EDGE_FOURIER, s);
+      HIPCHK(run_edge_gemm(b, g, EPI_EDGE, w.D3, s));
+    }
+    if (b->math == MATH_F32) {
+      {  // edge layer 2: M = SiLU(S W2^T + b2)
+        GemmArgs g = gargs((long)P * E, H, H, b->S, H, w.W2, b->M, H);
+        g.bias = w.b2; g.act = 1;
+        ProfScope ps(CHM_K_EDGE_MESSAGE, s);
+        HIPCHK(gemm(g, EPI_STD, s));
+      }
+      ProfScope ps(CHM_K_SEGMENT_MEAN, s);
+      HIPCHK(segment_mean(b->M, b->agg, b->n2g, b->node_off, b->edge_off, b->natoms, N, E, P, s));
+    } else {  // edge layer 2 fused with the aggregation: agg = mean_j SiLU(S W2^T + b2), M never stored
+      GemmArgs g = gargs((long)P * E, H, H, b->S, H, w.W2, nullptr, H);
+      g.bias = w.b2; g.act = 1; g.tiles = b->tiles; g.ntiles = b->ntiles; g.node_estart = b->node_estart;
+      g.natoms = b->natoms; g.n2g = b->n2g; g.agg = b->agg; g.nnodes = N; g.npairs = P; g.E = E;
+      ProfScope ps(CHM_K_EDGE_MESSAGE, s);
+      HIPCHK(run_edge_gemm(b, g, EPI_SEGMEAN, w.W23, s));
+    }
+  }
+  return CHM_OK;
+}
+
 // reuse_cond: the FiLM conditioning (cond_in + the conditioning MLP) of the previous call on this batch
 // is still valid (same t and text: the corrector call of a reverse step, chemeleon.py:438-448)
 static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, const float* lat, const float* temb,
@@ -1359,10 +1581,8 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
   const long N = b->N, E = b->E, R = (long)P * N;
   const int CIN = TD + X;
   ProfScope whole(CHM_K_DECODER, s);
-  // split16 node GEMMs: row maxima of their A operands, written by the producing kernels
-  const bool n16 = b->math == MATH_SPLIT16 && m->node16 && m->node_glds;
-  // pre-split node GEMMs: the producers write the A operands split (no row-max atomics then)
-  const bool ps = n16 && m->node_ps && b->Hs;
+  const EdgePlan ep = edge_plan(b, P);
+  const bool n16 = ep.n16, ps = ep.ps, pairs = ep.pairs, zero_grid = ep.zero_grid;
   const long RS = (long)b->P * N;
   auto rmx = [&](int k) { return n16 && !ps ? b->rmx + k * RS : nullptr; };
   if (m->film && !reuse_cond) {
@@ -1371,18 +1591,8 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
     g.bias = m->bc; g.act = 1;
     HIPCHK(run_gemm(b, g, EPI_STD, m->Wc3, s));
   }
-  // fc edge layer 1 on unordered pairs (option edge_pairs): F holds the pairs' features only
-  const bool pairs = b->math == MATH_SPLIT16 && m->edge_pairs && b->pe && !b->knn && E > 0;
-  // (edge layer 1 on pairs as two launches, the default below 256 row tiles: no intra-grid waits, nothing to clear;
-  // the memsets cost 4.8 us each per call, 0.9% of a 64x20 step)
-  // both edge layers on pairs in one grid (k_edge16_pairs_grid) for this call
-  const bool pair_grid = pairs && m->edge_pairs_layer && m->edge_rows && b->rtiles && m->edge_layer && b->psched &&
-                         P == b->P && b->nrt >= m->edge_layer_min && m->ncu > 0 && m->xcd_mask == 0xffu &&
-                         b->rt_nbig < 0;
-  const bool waits = !pairs || pair_grid;
-  // the pair grid's repair requests and per-layer flags start clear in every call: zeroed by the embedding launch
-  // below (two memset nodes less per call)
-  const bool zero_grid = b->xbad && b->math == MATH_SPLIT16 && pair_grid;
+  // (the pair grid's repair requests and per-layer flags start clear in every call: zeroed by the embedding launch
+  // below, two memset nodes less per call)
   // the embedding rows and the first kGBLayers layers' per-graph terms of edge layer 1 in one launch
   GraphBiasArgs ga0;
   const int nl0 = L < kGBLayers ? L : kGBLayers;
@@ -1394,12 +1604,7 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
                nl0 > 0 ? &ga0 : nullptr, nl0, 9, b->gbias, B, zero_grid ? b->xbad : nullptr,
                zero_grid ? 2L * kMaxLayers : 0L, zero_grid ? b->psched : nullptr,
                zero_grid ? (long)L * 8 * b->pplan.npx : 0L));
-  if (pairs)
-    HIPCHK(fourier_h(x, b->pi, b->pj, b->Ep, b->F, s, nullptr));  // (the (i, j) edges' features, i <= j)
-  else if (b->math == MATH_SPLIT16)
-    HIPCHK(fourier_h(x, b->ei, b->ej, E, b->F, s, b->knn ? b->fd : nullptr));  // fp16 hi/lo split rows
-  else
-    HIPCHK(fourier(x, b->ei, b->ej, E, b->F, s));
+  if (const int rc = edge_features(b, ep, x, s)) return rc;
   for (int l0 = kGBLayers; l0 < L; l0 += kGBLayers) {  // the per-graph terms of layers past the first 16
     GraphBiasArgs ga;
     const int nl = L - l0 < kGBLayers ? L - l0 : kGBLayers;
@@ -1409,15 +1614,7 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
     }
     HIPCHK(graph_bias(lat, ga, nl, 9, b->gbias + (size_t)l0 * B * H, B, s));
   }
-  if (b->xbad && b->math == MATH_SPLIT16 && waits && !pair_grid) {
-    // k_edge16_layer / k_edge16_tail: repair requests (layer l: xbad[l], tail of layer l: xbad[kMaxLayers + l])
-    // and row-tile flags start clear in every call (the flags also return to 0 at the end of every
-    // launch; this keeps a timed-out wait from leaking into later calls)
-    HIPCHK(hipMemsetAsync(b->xbad, 0, 2 * kMaxLayers * sizeof(unsigned), s));
-    if (!pairs && m->edge_rows && m->edge_layer && m->edge_dyn && b->sched)
-      HIPCHK(hipMemsetAsync(b->sched, 0, (size_t)L * (16 + 8 * b->sched_cap) * sizeof(unsigned), s));
-    if (!pairs && m->edge_rows && m->edge_layer) HIPCHK(hipMemsetAsync(b->lflags, 0, b->nrt * sizeof(unsigned), s));
-  }
+  if (const int rc = clear_edge_flags(b, ep, s, false)) return rc;
   for (int l = 0; l < L; ++l) {
     const LayerW& w = m->layers[l];
     if (m->film) {  // FiLM projection (cspnet.py:92)
@@ -1436,157 +1633,7 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
       if (ps) g.aex = b->Hle;
       HIPCHK(run_gemm(b, g, EPI_STD, w.WAB3, s, w.WAB16, w.WABsc));
     }
-    if (b->math == MATH_SPLIT16 && E == 0) {  // (knn: no atom within any other's radius: every mean is 0)
-      HIPCHK(hipMemsetAsync(b->agg, 0, (size_t)P * N * H * sizeof(float), s));
-      if (ps) {
-        HIPCHK(hipMemsetAsync(b->aggs, 0, (size_t)P * N * H * 4, s));
-        HIPCHK(hipMemsetAsync(b->agge, 0, (size_t)P * N * sizeof(int), s));
-      }
-    } else if (b->math == MATH_SPLIT16) {
-      // split16: fp16 hi/lo split rows throughout (edge16.hip). S lives in S's bytes as
-      // split rows [P*E][H/32][2][32] plus one packed exponent word per row (rowmax buffer).
-      int* sexp = reinterpret_cast<int*>(b->rowmax);
-      // edge layer 1: S_c = SiLU(D f_ij + P_c[i] + Q_c[j]), D f shared by the pair
-      EdgeArgs e1;
-      std::memset(&e1, 0, sizeof(e1));
-      e1.M = E; e1.N = H; e1.K = FD; e1.A = b->F; e1.W = w.D2h; e1.wscale = w.Dsc;
-      e1.ei = b->ei; e1.ej = b->ej; e1.PQ = b->PQ; e1.nnodes = N; e1.npairs = P; e1.E = E;
-      e1.node_off = b->node_off; e1.natoms = b->natoms; e1.n2g = b->n2g;
-      e1.S = b->S; e1.sexp = sexp; e1.dbg = m->edge_dbg; e1.stagger = m->edge_stagger;
-      // edge layer 2 fused with the aggregation: agg = mean_j SiLU(S W2^T + b2)
-      EdgeArgs e2;
-      std::memset(&e2, 0, sizeof(e2));
-      e2.M = (long)P * E; e2.N = H; e2.K = H; e2.A = b->S; e2.aexp = sexp;
-      e2.W = w.W22h16; e2.wscale = w.W2sc; e2.bias = w.b2; e2.tiles = b->tiles;
-      e2.ntiles = b->ntiles;
-      e2.node_estart = b->node_estart; e2.natoms = b->natoms; e2.n2g = b->n2g; e2.agg = b->agg;
-      e2.node_n = b->node_n; e2.agg_max = reinterpret_cast<unsigned*>(rmx(RMX_AGG));
-      if (ps) { e2.aggs = b->aggs; e2.agge = b->agge; }
-      e2.nnodes = N; e2.npairs = P; e2.E = E; e2.dbg = m->edge_dbg; e2.stagger = m->edge_stagger;
-      if (m->edge_rows && b->rtiles) {  // 256-row tiles, cut nodes continued across tiles
-        e2.rtiles = b->rtiles; e2.ntiles = (int)b->nrt; e2.sbuf = b->sbuf; e2.msgbuf = b->msgbuf;
-        e2.rinfo = b->rinfo; e2.rinfo_n = b->rinfo_n;
-        e2.rcnt = b->rcnt; e2.r2tot = b->r2tot;
-      }
-      // edge layer 2 on the two-launch schedule: one launch, or on a mixed row tiling (short_row_tiles) its 256-row
-      // tiles, then its 192-row tiles (k_edge16_short)
-      auto layer2 = [&](const EdgeArgs& ga) -> hipError_t {
-        if (!ga.rtiles || b->rt_nbig < 0) return edge_gemm16(ga, EPI_SEGMEAN, s);
-        if (b->rt_nbig > 0) {
-          EdgeArgs gb = ga;
-          gb.rt_count = (int)b->rt_nbig;
-          if (hipError_t r = edge_gemm16(gb, EPI_SEGMEAN, s); r != hipSuccess) return r;
-        }
-        EdgeArgs gs = ga;
-        gs.rt_first = (int)b->rt_nbig;
-        gs.rt_count = (int)(b->nrt - b->rt_nbig);
-        gs.rt_h = kShortRows;
-        gs.rt_e0 = b->rt_nbig * kTileRows;
-        return edge_gemm16(gs, EPI_SEGMEAN, s);
-      };
-      // (instrumented eager launches keep one launch per layer, so the per-kernel timings stay whole;
-      // captured launches are never instrumented)
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      const bool instrumented = g_prof_on && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
-      // (same-box A/B, static grid against two launches: 64x40 8.47 -> 7.77 ms per step, 512x40 54.9 -> 54.8,
-      // 64x20 2.95 -> 3.10: 100 row tiles leave each XCD's job list too short to pack; profiles/r5/grid/)
-      if (pair_grid) {
-        // both edge layers in one grid, layer 1 on pairs (k_edge16_pairs_grid)
-        EdgeArgs e1p = e1;
-        e1p.M = b->Ep; e1p.Mp = b->Ep; e1p.pi = b->pi; e1p.pj = b->pj; e1p.pe = b->pe; e1p.pnode = b->pnode;
-        e1p.xbad = e2.xbad = b->xbad + l;
-        PairSched ps;
-        ps.jobs = b->pjobs; ps.jstride = b->pplan.jstride;
-        ps.npx = b->pplan.npx; ps.pflag = b->psched + (size_t)l * 8 * b->pplan.npx; ps.R = b->nrt;
-        ProfScope ps_(CHM_K_EDGE_LAYER, s);
-        // (CHM_EDGE_TRACE_LAYER=4: block timelines of this grid, slot = blockIdx)
-        HIPCHK(traced_edge_launch(m, e2, 4, E, s, [&] {
-          ps.trace = e2.trace;
-          e2.trace = nullptr;
-          const hipError_t r = edge_gemm16_pairs_layer(e1p, e2, ps, m->repair_grid, s);
-          ps.trace = nullptr;
-          return r;
-        }));
-      } else if (pairs) {
-        // edge layer 1 on pairs (both directions' S rows per pair), then edge layer 2 on its row tiles
-        EdgeArgs e1p = e1;
-        e1p.M = b->Ep; e1p.Mp = b->Ep; e1p.pi = b->pi; e1p.pj = b->pj; e1p.pe = b->pe; e1p.pnode = b->pnode;
-        {
-          ProfScope ps(CHM_K_EDGE_FOURIER, s);
-          HIPCHK(edge_gemm16_pairs(e1p, s));
-        }
-        ProfScope ps(CHM_K_EDGE_MESSAGE, s);
-        HIPCHK(layer2(e2));
-      } else if (e2.rtiles && m->edge_layer && b->nrt >= m->edge_layer_min && b->rt_nbig < 0 &&
-                 (!m->edge_trace || m->edge_trace_layer == 3)) {
-        // both layers in one grid: layer 2's row tiles behind layer 1's (k_edge16_layer)
-        e1.lflags = e2.lflags = b->lflags;
-        e1.xbad = e2.xbad = b->xbad + l;
-        ProfScope ps(CHM_K_EDGE_LAYER, s);
-        // (CHM_EDGE_TRACE_LAYER=3: block timelines of this grid, slot = blockIdx)
-        HIPCHK(traced_edge_launch(m, e1, 3, E, s, [&] {
-          e2.trace = e1.trace;
-          const hipError_t r =
-              m->ncu > 0 && m->xcd_mask == 0xffu &&
-                      (m->edge_dyn == 2 || (m->edge_dyn == 1 && b->nrt >= kDynMinTiles))
-                  ? edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s,
-                                      b->sched + (size_t)l * (16 + 8 * b->sched_cap), (int)b->sched_cap, m->ncu,
-                                      m->edge_pool, m->edge_skip_xcd)
-                  : edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s);
-          e2.trace = nullptr;
-          return r;
-        }));
-      } else if (b->l1_rows_a > 0 && b->xbad && m->edge_split && !instrumented && !m->edge_trace) {
-        // Edge layer 1 in whole rounds of the grid (rows [0, l1_rows_a)), then one grid with its
-        // partial last round first and all of edge layer 2's segment tiles behind it (the few that
-        // read those rows wait for them inside the grid). Same tiles, same arithmetic: bit-identical
-        // to one launch per layer.
-        EdgeArgs e1b = e1;
-        e1.M = b->l1_rows_a;
-        e1.zero_flags = b->tail_flags;
-        e1.nzero = (int)((E - b->l1_rows_a + kTileRows - 1) / kTileRows);
-        e1b.row_base = b->l1_rows_a;
-        e1b.flags = e2.flags = b->tail_flags;
-        e1b.flag_row0 = e2.flag_row0 = b->l1_rows_a;
-        e2.xbad = b->xbad + kMaxLayers + l;  // (a timed-out wait: the repair launches recompute edge layer 2)
-        HIPCHK(edge_gemm16(e1, EPI_EDGE, s));
-        HIPCHK(edge_gemm16_tail(e1b, e2, m->repair_grid, s));
-      } else {
-        {
-          ProfScope ps(CHM_K_EDGE_FOURIER, s);
-          HIPCHK(traced_edge_launch(m, e1, 1, E, s, [&] {
-            return edge_gemm16(e1, EPI_EDGE, s);
-          }));
-        }
-        ProfScope ps(CHM_K_EDGE_MESSAGE, s);
-        HIPCHK(traced_edge_launch(m, e2, 2, E, s, [&] {
-          return layer2(e2);
-        }));
-      }
-    } else {
-      {  // edge layer 1: S_c = SiLU(D f_ij + P_c[i] + Q_c[j]), D f shared by the pair
-        GemmArgs g = gargs(E, H, FD, b->F, FD, w.D, b->S, H);
-        g.ei = b->ei; g.ej = b->ej; g.PQ = b->PQ; g.nnodes = N; g.npairs = P; g.E = E;
-        ProfScope ps(CHM_K_EDGE_FOURIER, s);
-        HIPCHK(run_edge_gemm(b, g, EPI_EDGE, w.D3, s));
-      }
-      if (b->math == MATH_F32) {
-        {  // edge layer 2: M = SiLU(S W2^T + b2)
-          GemmArgs g = gargs((long)P * E, H, H, b->S, H, w.W2, b->M, H);
-          g.bias = w.b2; g.act = 1;
-          ProfScope ps(CHM_K_EDGE_MESSAGE, s);
-          HIPCHK(gemm(g, EPI_STD, s));
-        }
-        ProfScope ps(CHM_K_SEGMENT_MEAN, s);
-        HIPCHK(segment_mean(b->M, b->agg, b->n2g, b->node_off, b->edge_off, b->natoms, N, E, P, s));
-      } else {  // edge layer 2 fused with the aggregation: agg = mean_j SiLU(S W2^T + b2), M never stored
-        GemmArgs g = gargs((long)P * E, H, H, b->S, H, w.W2, nullptr, H);
-        g.bias = w.b2; g.act = 1; g.tiles = b->tiles; g.ntiles = b->ntiles; g.node_estart = b->node_estart;
-        g.natoms = b->natoms; g.n2g = b->n2g; g.agg = b->agg; g.nnodes = N; g.npairs = P; g.E = E;
-        ProfScope ps(CHM_K_EDGE_MESSAGE, s);
-        HIPCHK(run_edge_gemm(b, g, EPI_SEGMEAN, w.W23, s));
-      }
-    }
+    if (const int rc = edge_block(b, P, l, ep, ps, s)) return rc;
     {  // node MLP 1: U = SiLU([Hl | agg] W3^T + b3)
       GemmArgs g = gargs(R, H, 2 * H, b->Hl, H, w.W3, b->Y, H);
       g.A2 = b->agg; g.lda2 = H; g.ksplit = H; g.bias = w.b3; g.act = 1;
@@ -1956,6 +2003,63 @@ extern "C" int chm_debug_gemm(const chm_debug_gemm_args* a, void* stream) {
   e = node_gemm(g, s);
   g_node_rows = r0; g_node_cols = c0; g_node_blocks = b0;
   return done(e, "node_gemm");
+}
+
+// The message path of one CSP layer (edge_block, the code run_decoder runs, on the schedule the model's options and the
+// batch give it) on caller operands (tests/test_gpu_edge_layer.py). Every argument check runs before the first HIP
+// call, the batch-independent ones first, so a refused call needs no device.
+extern "C" int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac, int64_t n_frac,
+                                    const float* d_PQ, int64_t n_pq, float* d_agg, int64_t n_agg, void* d_agg_split,
+                                    int32_t* d_agg_exp, void* stream) {
+  auto bad = [&](const char* field, const std::string& why) {
+    return fail(CHM_E_ARG, std::string("chm_debug_edge_layer: ") + field + " " + why);
+  };
+  if (!d_frac) return bad("d_frac", "is NULL");
+  if (!d_PQ) return bad("d_PQ", "is NULL");
+  if (!d_agg) return bad("d_agg", "is NULL");
+  if ((d_agg_split == nullptr) != (d_agg_exp == nullptr))
+    return bad(d_agg_split ? "d_agg_exp" : "d_agg_split", "is NULL (the split rows and their exponents go together)");
+  if (pairs < 1) return bad("pairs", "must be in [1, max_pairs]");
+  if (layer < 0) return bad("layer", "must be in [0, num_layers)");
+  if (n_frac < 3 || n_frac % 3) return bad("n_frac", "must be 3 N, N >= 1");
+  const int64_t Nc = n_frac / 3;
+  if (n_pq != (int64_t)pairs * Nc * 2 * H)
+    return bad("n_pq", "is " + std::to_string(n_pq) + ", [pairs, N, 2H] has " + std::to_string((int64_t)pairs * Nc * 2 * H));
+  if (n_agg != (int64_t)pairs * Nc * H)
+    return bad("n_agg", "is " + std::to_string(n_agg) + ", [pairs, N, H] has " + std::to_string((int64_t)pairs * Nc * H));
+  for (const void* p : {(const void*)d_frac, (const void*)d_PQ, (const void*)d_agg, (const void*)d_agg_split,
+                        (const void*)d_agg_exp})
+    if ((uintptr_t)p % 16) return bad("operands", "must be 16-byte aligned");
+  if (!b) return bad("batch", "is NULL");
+  const chm_model* m = b->m;
+  if (b->knn) return fail(CHM_E_UNSUPPORTED, "chm_debug_edge_layer: batch is a knn batch (fc batches only)");
+  if (Nc != b->N) return bad("n_frac", "is " + std::to_string(n_frac) + ", the batch needs " + std::to_string(3 * b->N));
+  if (pairs > b->P) return bad("pairs", "must be in [1, max_pairs]");
+  if (layer >= m->d.num_layers) return bad("layer", "must be in [0, num_layers)");
+  const long N = b->N;
+  const EdgePlan ep = edge_plan(b, pairs);
+  if (d_agg_split && !ep.ps)
+    return fail(CHM_E_UNSUPPORTED, "chm_debug_edge_layer: d_agg_split needs a split16 batch created with option node_ps");
+
+  hipStream_t s = (hipStream_t)stream;
+  auto run = [&](bool ps) -> int {
+    if (const int rc = clear_edge_flags(b, ep, s, true)) return rc;
+    if (ep.n16 && !ps)  // (film_ln zeroes agg's row maxima for the layer's atomic maxima)
+      HIPCHK(hipMemsetAsync(b->rmx + RMX_AGG * (long)b->P * N, 0, (size_t)b->P * N * sizeof(float), s));
+    return edge_block(b, pairs, layer, ep, ps, s);
+  };
+  if (const int rc = edge_features(b, ep, d_frac, s)) return rc;
+  HIPCHK(hipMemcpyAsync(b->PQ, d_PQ, (size_t)n_pq * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // fp32 agg: the block without pre-split (a pre-split batch writes agg only as split rows: the block runs once more)
+  if (const int rc = run(false)) return rc;
+  HIPCHK(hipMemcpyAsync(d_agg, b->agg, (size_t)n_agg * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (d_agg_split) {
+    if (const int rc = run(true)) return rc;
+    HIPCHK(hipMemcpyAsync(d_agg_split, b->aggs, (size_t)pairs * N * H * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_agg_exp, b->agge, (size_t)pairs * N * sizeof(int), hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return CHM_OK;
 }
 
 extern "C" int chm_edge_features(chm_batch* b, const float* x, float* feat, void* stream) {

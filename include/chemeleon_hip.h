@@ -368,6 +368,21 @@ typedef struct chm_debug_gemm_args {
 } chm_debug_gemm_args;
 int chm_debug_gemm(const chm_debug_gemm_args* args, void* stream);
 
+/* Test hook: the message path of CSP layer `layer` on caller operands, by the code and on the schedule a decoder
+ * call on this fc batch takes (the model's math mode and options, the batch's tables):
+ *   agg[c][i] = mean_j SiLU(SiLU(D f_ij + P_c[i] + Q_c[j]) W2^T + b2).
+ * d_frac [N,3]: the Fourier features are written from it as the decoder writes them. d_PQ [pairs,N,2H]: per node
+ * [P | Q], P already holding b1 + the per-graph term; copied into the batch's buffer. d_agg [pairs,N,H] fp32.
+ * d_agg_split / d_agg_exp (both or neither; a split16 batch created with option node_ps only): the layer's output
+ * as the pre-split node GEMMs read it, split rows [pairs*N][H/16][hi 16 | lo 16] fp16 (pairs*N*H*4 bytes) and per
+ * row the packed int8 exponents of its four 128-column chunks; d_agg then comes from a run of the block without
+ * pre-split. Clears the schedule's flag words as a decoder call does, synchronises the stream. Every argument
+ * check runs before any HIP call (CHM_E_ARG / CHM_E_UNSUPPORTED naming the field, without a device); knn
+ * batches are refused. */
+int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac, int64_t n_frac, const float* d_PQ,
+                         int64_t n_pq, float* d_agg, int64_t n_agg, void* d_agg_split, int32_t* d_agg_exp,
+                         void* stream);
+
 /* Host-only test hook (no device): the row tiles edge layer 2 runs on for an fc batch of these
  * crystals (EdgeArgs::rtiles; DESIGN.md "Edge layer 2 on row tiles"). Returns the tile count R (or a
  * negative CHM_E_*); if out4 holds >= 4 R int32 it receives per tile {first node starting in the tile,

@@ -198,6 +198,15 @@ def _ln(x, sd, p):
     return F.layer_norm(x, (x.shape[-1],), sd[p + ".weight"], sd[p + ".bias"], 1e-5)
 
 
+def csp_messages(sd, p, hl, edges, llt_e, feats):
+    """CSPLayer.edge_model + the aggregation of node_model, cspnet.py:134-160: the edge MLP over
+    [h_i | h_j | lattice inner products | Fourier features], then the mean of each source node's messages."""
+    ein = torch.cat([hl[edges[0]], hl[edges[1]], llt_e, feats], dim=1)  # :138-150
+    m = F.silu(F.linear(ein, sd[p + "edge_mlp.0.weight"], sd[p + "edge_mlp.0.bias"]))
+    m = F.silu(F.linear(m, sd[p + "edge_mlp.2.weight"], sd[p + "edge_mlp.2.bias"]))
+    return scatter_mean(m, edges[0], hl.shape[0])  # :155-160
+
+
 def cspnet_forward(sd: Dict[str, torch.Tensor], cfg: Dict, atom_types, frac_coords, lattices,
                    num_atoms, node2graph, t_emb=None, text=None, hidden: Optional[List] = None):
     """cspnet.py:345-405 (ln, ip, smooth=False; cfg["edge_style"] "fc" (default) or "knn").
@@ -234,10 +243,7 @@ def cspnet_forward(sd: Dict[str, torch.Tensor], cfg: Dict, atom_types, frac_coor
         p = f"csp_layer_{i}."
         hin = h  # CSPLayer.forward, :165-181
         hl = _ln(hin, sd, p + "layer_norm")
-        ein = torch.cat([hl[edges[0]], hl[edges[1]], llt[e2g], feats], dim=1)  # :138-150
-        m = silu(F.linear(ein, sd[p + "edge_mlp.0.weight"], sd[p + "edge_mlp.0.bias"]))
-        m = silu(F.linear(m, sd[p + "edge_mlp.2.weight"], sd[p + "edge_mlp.2.bias"]))
-        agg = scatter_mean(m, edges[0], hl.shape[0])  # :155-160
+        agg = csp_messages(sd, p, hl, edges, llt[e2g], feats)
         nin = torch.cat([hl, agg], dim=1)
         o = silu(F.linear(nin, sd[p + "node_mlp.0.weight"], sd[p + "node_mlp.0.bias"]))
         o = silu(F.linear(o, sd[p + "node_mlp.2.weight"], sd[p + "node_mlp.2.bias"]))

@@ -63,6 +63,9 @@ def test_null_handles_are_rejected():
     assert lib.chm_batch_info(None, None, None, None, None) == -1
     assert lib.chm_d3pm_sample(-1, 104, 100, *([None] * 8)) == -1
     assert lib.chm_batch_num_nodes(None) == -1
+    x = ctypes.c_void_p(0x10000)  # (never dereferenced: the NULL batch is refused before any HIP call)
+    assert lib.chm_debug_edge_layer(None, 1, 0, x, 3, x, 1024, x, 512, None, None, None) == -1
+    assert b"batch" in lib.chm_last_error()
 
 
 def test_cpu_tensors_are_refused():
