@@ -57,6 +57,15 @@ class chm_step_io(ctypes.Structure):
                 ("d_rand_x2", c_void_p), ("n_rand_x2", c_i64)]
 
 
+class chm_constraint(ctypes.Structure):
+    """The known entries of a constrained reverse step with their element counts (include/chemeleon_hip.h)."""
+    _fields_ = [("d_a0", c_void_p), ("n_a0", c_i64), ("d_type_mask", c_void_p), ("n_type_mask", c_i64),
+                ("d_x0", c_void_p), ("n_x0", c_i64), ("d_frac_mask", c_void_p), ("n_frac_mask", c_i64),
+                ("d_l0", c_void_p), ("n_l0", c_i64), ("d_lattice_mask", c_void_p), ("n_lattice_mask", c_i64),
+                ("d_fwd", c_void_p), ("n_fwd", c_i64), ("d_rand_a", c_void_p), ("n_rand_a", c_i64),
+                ("d_rand_l", c_void_p), ("n_rand_l", c_i64), ("d_rand_x", c_void_p), ("n_rand_x", c_i64)]
+
+
 class chm_debug_gemm_args(ctypes.Structure):
     """One GEMM kernel on caller operands (test hook chm_debug_gemm, include/chemeleon_hip.h)."""
     _fields_ = [("kind", ctypes.c_int32), ("act", ctypes.c_int32), ("M", c_i64), ("N", ctypes.c_int32),
@@ -159,7 +168,12 @@ SIGNATURES = {
                                    ctypes.POINTER(chm_step_io), c_u64, c_i64, c_i64, c_void_p]),
     "chm_sample_step_dt_noise": (c_int, [c_void_p, ctypes.POINTER(chm_schedule), c_void_p, c_float,
                                          ctypes.POINTER(chm_step_io), c_void_p]),
-    "chm_segment_mean": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    "chm_sample_step_con": (c_int, [c_void_p, ctypes.POINTER(chm_schedule), c_int, c_void_p, c_float,
+                                    ctypes.POINTER(chm_step_io), ctypes.POINTER(chm_constraint), c_u64, c_i64, c_i64,
+                                    c_void_p]),
+    "chm_constrain_state": (c_int, [c_void_p, ctypes.POINTER(chm_schedule), ctypes.POINTER(chm_constraint), c_int,
+                                    c_void_p, c_int, ctypes.POINTER(chm_step_io), c_u64, c_i64, c_i64, c_void_p]),
+    "chm_segment_mean": (c_int,[c_void_p, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "chm_d3pm_sample": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
     "chm_edge_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

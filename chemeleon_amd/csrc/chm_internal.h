@@ -297,5 +297,23 @@ hipError_t d3pm_sample(int N, int A, int T, const float* logits, long ld_logits,
                        const float* q1, const float* qm, int64_t* out, uint64_t seed, int64_t node_base,
                        hipStream_t s, int* bad = nullptr);  // bad: see k_d3pm (caller indices checked)
 
+// constrained sampling (constrain.hip): the known entries of the state at their forward-noised level-s values
+struct ConstrainArgs {
+  long N; int B, A, T;
+  int level;                       // s, or with d_t set: s = *d_t - 1 (the step's t read on the device)
+  const int* d_t;
+  const int64_t* a0; const unsigned char* type_mask;     // [N], [N]
+  const float* x0; const unsigned char* frac_mask;       // [N,3], [N]
+  const float* l0; const unsigned char* lattice_mask;    // [B,3,3], [B]
+  const float* fwd;                // [T+1][4]: sqrt(abar), sqrt(1 - abar), sigma_x, sigma_norm
+  const float* q_mats;             // [T+1][A][A]
+  int64_t* a; float* x; float* l;  // the state, updated in place
+  const float *ra, *rl, *rx;       // caller noise [N,A], [B,3,3], [N,3], or null: Philox kinds 4, 5, 6
+  uint64_t seed; int64_t node_base, graph_base;
+  long node_blocks;                // (set by the launcher)
+};
+// what: bit 0 types, bit 1 lattices, bit 2 coordinates (fields without a mask are skipped)
+hipError_t constrain(const ConstrainArgs& g, int what, hipStream_t s);
+
 }  // namespace chm
 

@@ -1720,9 +1720,62 @@ static int check_step_io(const chm_batch* b, const chm_step_io* io, bool noise_r
   return CHM_OK;
 }
 
+// the buffers of a constraint against the batch (N nodes, B crystals, A classes) and the schedule's T
+static int check_constraint(const chm_batch* b, const chm_schedule* sc, const chm_constraint* con) {
+  if (!con) return fail(CHM_E_ARG, "constraint is NULL");
+  const long N = b->N, B = b->B, A = b->m->d.max_atoms;
+  auto sized = [&](const void* p, int64_t n, long expect, const char* name) -> int {
+    if (p && n != expect)
+      return fail(CHM_E_ARG, std::string("constraint ") + name + ": " + std::to_string(n) +
+                                 " elements, the batch needs " + std::to_string(expect));
+    return CHM_OK;
+  };
+  auto pair = [&](const void* v, const void* m, const char* name) -> int {
+    if ((v != nullptr) != (m != nullptr))
+      return fail(CHM_E_ARG, std::string("constraint ") + name + ": known values and mask are given together or not at all");
+    return CHM_OK;
+  };
+  int rc;
+  if ((rc = pair(con->d_a0, con->d_type_mask, "a0 / type_mask"))) return rc;
+  if ((rc = pair(con->d_x0, con->d_frac_mask, "x0 / frac_mask"))) return rc;
+  if ((rc = pair(con->d_l0, con->d_lattice_mask, "l0 / lattice_mask"))) return rc;
+  if ((rc = sized(con->d_a0, con->n_a0, N, "a0 [N]"))) return rc;
+  if ((rc = sized(con->d_type_mask, con->n_type_mask, N, "type_mask [N]"))) return rc;
+  if ((rc = sized(con->d_x0, con->n_x0, 3 * N, "x0 [N,3]"))) return rc;
+  if ((rc = sized(con->d_frac_mask, con->n_frac_mask, N, "frac_mask [N]"))) return rc;
+  if ((rc = sized(con->d_l0, con->n_l0, 9 * B, "l0 [B,3,3]"))) return rc;
+  if ((rc = sized(con->d_lattice_mask, con->n_lattice_mask, B, "lattice_mask [B]"))) return rc;
+  if (!con->d_fwd) return fail(CHM_E_ARG, "constraint fwd is NULL");
+  if (con->n_fwd != 4L * (sc->T + 1))
+    return fail(CHM_E_ARG, "constraint fwd [T+1,4]: " + std::to_string(con->n_fwd) + " elements, the schedule's T = " +
+                               std::to_string(sc->T) + " needs " + std::to_string(4L * (sc->T + 1)));
+  const int given = (con->d_rand_a != nullptr) + (con->d_rand_l != nullptr) + (con->d_rand_x != nullptr);
+  if (given != 0 && given != 3) return fail(CHM_E_ARG, "constraint noise: all three buffers or none");
+  if ((rc = sized(con->d_rand_a, con->n_rand_a, N * A, "rand_a [N,A]"))) return rc;
+  if ((rc = sized(con->d_rand_l, con->n_rand_l, 9 * B, "rand_l [B,3,3]"))) return rc;
+  if ((rc = sized(con->d_rand_x, con->n_rand_x, 3 * N, "rand_x [N,3]"))) return rc;
+  return CHM_OK;
+}
+
+static ConstrainArgs constrain_args(const chm_batch* b, const chm_schedule* sc, const chm_constraint* con, int level,
+                                    const int* d_t, const chm_step_io* io, uint64_t seed, int64_t node_base,
+                                    int64_t graph_base) {
+  ConstrainArgs c;
+  std::memset(&c, 0, sizeof(c));
+  c.N = b->N; c.B = b->B; c.A = b->m->d.max_atoms; c.T = sc->T; c.level = level; c.d_t = d_t;
+  c.a0 = con->d_a0; c.type_mask = con->d_type_mask; c.x0 = con->d_x0; c.frac_mask = con->d_frac_mask;
+  c.l0 = con->d_l0; c.lattice_mask = con->d_lattice_mask; c.fwd = con->d_fwd; c.q_mats = sc->d_q_mats;
+  c.a = io->d_atom_types; c.x = io->d_frac; c.l = io->d_lattices;
+  c.ra = con->d_rand_a; c.rl = con->d_rand_l; c.rx = con->d_rand_x;
+  c.seed = seed; c.node_base = node_base; c.graph_base = graph_base;
+  return c;
+}
+
+// con != null (chm_sample_step_con): the known entries are replaced at level t - 1 between the predictor and the
+// corrector's decoder call (stage 1) and the known coordinates again behind the corrector (stage 2, same noise)
 static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, float cond_scale, const chm_step_io* io,
                        bool noise_required, bool noise_allowed, uint64_t seed, int64_t node_base, int64_t graph_base,
-                       hipStream_t s) {
+                       hipStream_t s, const chm_constraint* con = nullptr) {
   if (!b || !sc) return fail(CHM_E_ARG, "batch / schedule is NULL");
   if (b->P < 2) return fail(CHM_E_ARG, "sampling needs a batch created with max_pairs = 2");
   if (!b->m->film) return fail(CHM_E_ARG, "sampling needs a time-conditioned decoder (time_dim > 0)");
@@ -1736,6 +1789,7 @@ static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, fl
                                std::to_string(b->m->d.max_atoms) + " / " + std::to_string(b->m->d.time_dim));
   int rc = check_step_io(b, io, noise_required, noise_allowed);
   if (rc) return rc;
+  if (con && (rc = check_constraint(b, sc, con))) return rc;
   const bool host_noise = io->d_rand_a != nullptr;
   int64_t* d_a = io->d_atom_types;
   float *d_x = io->d_frac, *d_l = io->d_lattices;
@@ -1753,10 +1807,16 @@ static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, fl
   if (host_noise) { sa.ra = io->d_rand_a; sa.rl = io->d_rand_l; sa.rx1 = io->d_rand_x1; sa.rx2 = io->d_rand_x2; }
   sa.seed = seed; sa.node_base = node_base; sa.graph_base = graph_base;
   HIPCHK(step_predictor(sa, s));
+  ConstrainArgs ca;
+  if (con) {  // stage 1: the corrector's decoder call sees the known entries at level t - 1
+    ca = constrain_args(b, sc, con, t - 1, d_t, io, seed, node_base, graph_base);
+    HIPCHK(constrain(ca, 7, s));
+  }
   // corrector: same t and text as the predictor, so its FiLM conditioning is reused
   rc = run_decoder(b, 2, d_a, d_x, d_l, temb, 0, d_t, d_cond, d_null, 1, s, true);
   if (rc) return rc;
   HIPCHK(step_corrector(sa, s));
+  if (con) HIPCHK(constrain(ca, 4, s));  // stage 2: the corrector's move on the known coordinates is discarded
   if (d_t) HIPCHK(decrement(d_t, s));
   return CHM_OK;
 }
@@ -1777,6 +1837,46 @@ extern "C" int chm_sample_step_dt_noise(chm_batch* b, const chm_schedule* sc, in
                                         const chm_step_io* io, void* stream) {
   if (!d_t) return fail(CHM_E_ARG, "d_t is NULL");
   return sample_step(b, sc, 0, d_t, cond_scale, io, true, true, 0, 0, 0, (hipStream_t)stream);
+}
+
+extern "C" int chm_sample_step_con(chm_batch* b, const chm_schedule* sc, int t, int32_t* d_t, float cond_scale,
+                                   const chm_step_io* io, const chm_constraint* con, uint64_t seed, int64_t node_base,
+                                   int64_t graph_base, void* stream) {
+  if (!b || !sc) return fail(CHM_E_ARG, "batch / schedule is NULL");
+  if (!con) return fail(CHM_E_ARG, "constraint is NULL (chm_sample_step is the unconstrained step)");
+  return sample_step(b, sc, d_t ? 0 : t, d_t, cond_scale, io, false, true, seed, node_base, graph_base,
+                     (hipStream_t)stream, con);
+}
+
+extern "C" int chm_constrain_state(chm_batch* b, const chm_schedule* sc, const chm_constraint* con, int level,
+                                   const int32_t* d_t, int what, const chm_step_io* io, uint64_t seed,
+                                   int64_t node_base, int64_t graph_base, void* stream) {
+  if (!b || !sc) return fail(CHM_E_ARG, "batch / schedule is NULL");
+  if (sc->T < 1) return fail(CHM_E_ARG, "schedule: T must be >= 1");
+  if (!sc->d_q_mats) return fail(CHM_E_ARG, "NULL schedule table");
+  if (sc->num_classes != b->m->d.max_atoms)
+    return fail(CHM_E_ARG, "schedule: num_classes " + std::to_string(sc->num_classes) + " does not match the model's " +
+                               std::to_string(b->m->d.max_atoms));
+  if (!d_t && (level < 0 || level > sc->T))
+    return fail(CHM_E_ARG, "level " + std::to_string(level) + " outside [0, " + std::to_string(sc->T) + "]");
+  if (what < 1 || what > 7) return fail(CHM_E_ARG, "what " + std::to_string(what) + " outside [1, 7]");
+  if (!io) return fail(CHM_E_ARG, "io is NULL");
+  const long N = b->N, B = b->B;
+  auto want = [&](const void* p, int64_t n, long expect, const char* name) -> int {
+    if (!p) return fail(CHM_E_ARG, std::string(name) + " is NULL");
+    if (n != expect)
+      return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " elements, the batch needs " +
+                                 std::to_string(expect));
+    return CHM_OK;
+  };
+  int rc;
+  if ((rc = want(io->d_atom_types, io->n_atom_types, N, "atom_types [N]"))) return rc;
+  if ((rc = want(io->d_frac, io->n_frac, 3 * N, "frac [N,3]"))) return rc;
+  if ((rc = want(io->d_lattices, io->n_lattices, 9 * B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check_constraint(b, sc, con))) return rc;
+  const ConstrainArgs ca = constrain_args(b, sc, con, level, d_t, io, seed, node_base, graph_base);
+  HIPCHK(constrain(ca, what, (hipStream_t)stream));
+  return CHM_OK;
 }
 
 extern "C" int chm_segment_mean(chm_batch* b, int pairs, const float* msg, int64_t msg_count, float* agg,
@@ -1835,7 +1935,7 @@ extern "C" int chm_d3pm_sample(int N, int A, int T, const float* logits, const i
 
 extern "C" int chm_debug_philox(uint64_t seed, int t, int kind, int64_t base, int64_t n, int normal, float* out,
                                 void* stream) {
-  if (n < 0 || !out || kind < 0 || kind > 3) return fail(CHM_E_ARG, "bad arguments");
+  if (n < 0 || !out || kind < 0 || kind > 6) return fail(CHM_E_ARG, "bad arguments");
   HIPCHK(philox_fill(seed, t, kind, base, n, normal, out, (hipStream_t)stream));
   return CHM_OK;
 }

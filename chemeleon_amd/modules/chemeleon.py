@@ -171,6 +171,14 @@ class Chemeleon(nn.Module):
             self._tables[key] = (tt, (coef, q1, qm))
         return self._tables[key]
 
+    def _constraint_args(self, constraint, natoms, noise=None):
+        """(chm_constraint, keepalive) of `constraint` for these crystals on the model's device, with the
+        forward table {sqrt(abar_t), sqrt(1 - abar_t), sigma_t, sigmas_norm_t} of the training forward (the one
+        cached entry of _train_tables, built once per model and device)."""
+        constraint.check_batch(natoms, self.max_atoms)
+        _tt, (coef, _q1, _qm) = self._train_tables()
+        return constraint.to_device(self.device, fwd=coef, noise=noise)
+
     @staticmethod
     def _build_text_encoder(cfg, kwargs):
         """reference chemeleon.py:37-52, from local files only; None when no
@@ -314,7 +322,7 @@ class Chemeleon(nn.Module):
                       node_base: int = 0, graph_base: int = 0,
                       init: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                       graph: Optional[bool] = None, lanes: int = 1,
-                      global_sizes: Optional[Tuple[int, int]] = None) -> Iterator[Tuple]:
+                      global_sizes: Optional[Tuple[int, int]] = None, constraint=None) -> Iterator[Tuple]:
         """Reverse loop of chemeleon.py:305-467 yielding device tensors
         (t, atom_types [N], frac_coords [N,3] in [0,1), lattices [B,3,3]),
         starting with the pure-noise state at t = T.
@@ -350,7 +358,18 @@ class Chemeleon(nn.Module):
         group's GEMM epilogues (store bursts, VALU) overlap the other's matrix
         work instead of every CU reaching its epilogue at the same moment.
         Results are bit-identical: Philox noise is keyed by global node / graph
-        index and crystals never interact."""
+        index and crystals never interact.
+
+        constraint (chemeleon_amd.Constraint for exactly these crystals): the atom types, coordinates and
+        lattices it marks are held. After every reverse step t -> t-1 they are replaced by their known values
+        forward-noised to level t-1 (chm_sample_step_con: once between predictor and corrector, the coordinates
+        again behind the corrector), so the final state holds them exactly (lattices times the lattice mask,
+        coordinates % 1.0) and the rest is generated around them. The replacement's noise is always device
+        Philox keyed by `seed` (streams 4-6), in both noise modes: with noise="torch" the CPU generator is
+        consumed exactly as in an unconstrained run and crystals without known entries keep the reference's
+        trajectory. Works eagerly and as a captured graph (fc batches), eagerly on knn batches; lanes > 1 is
+        refused. Without a constraint the enqueued work is exactly the unconstrained step's. Sampling over
+        ranks (sample_states_distributed) does not shard a constraint and refuses the keyword."""
         if isinstance(natoms, int):
             natoms = [natoms]
         natoms = [int(n) for n in natoms]
@@ -360,6 +379,10 @@ class Chemeleon(nn.Module):
             raise ValueError("natoms and texts must have the same number of elements.")
         if noise not in ("torch", "philox"):
             raise ValueError("noise must be 'torch' or 'philox'")
+        if constraint is not None:
+            if lanes > 1:
+                raise ValueError("a constraint cannot be split over lanes: lanes must be 1")
+            constraint.check_batch(natoms, self.max_atoms)
         knn = getattr(self.decoder, "edge_style", "fc") == "knn"
         if graph is None:  # knn edges are rebuilt from the coordinates with a host sync: eager only
             graph = not knn
@@ -399,13 +422,14 @@ class Chemeleon(nn.Module):
         batch = self.decoder.hip_batch(natoms, max_pairs=2)
         L = _lib.load()
         stream = _lib.stream_handle(dev)
+        con, _con_keep = (None, None) if constraint is None else self._constraint_args(constraint, natoms)
         emit = (lambda *ts: tuple(t.clone() for t in ts)) if clone else (lambda *ts: ts)
         yield (T,) + emit(a, x, lat)
         if graph and noise == "torch":
             if lanes > 1:
                 raise ValueError("lanes > 1 needs noise='philox'")
             yield from self._replay_torch_noise(batch, sched, a, x, lat, cond, null, cond_scale, step_noise, T, t_stop,
-                                                emit)
+                                                emit, con, seed, node_base, graph_base)
             return
         if graph:
             from ..distributed import partition
@@ -434,6 +458,11 @@ class Chemeleon(nn.Module):
                         io = _lib.step_io(a, x, lat, cond, null, node0=n0, graph0=g0, nodes=noff[g1] - n0,
                                           graphs=g1 - g0)
                         with torch.cuda.stream(st):
+                            if con is not None:  # (one lane: the whole batch)
+                                _lib.check(L.chm_sample_step_con(
+                                    bk.handle, sched, 0, _lib.ptr(d_t), float(cond_scale), io, con, seed, node_base,
+                                    graph_base, _lib.stream_handle(dev)), "chm_sample_step_con")
+                                continue
                             _lib.check(L.chm_sample_step_dt(
                                 bk.handle, sched, _lib.ptr(d_t, 4 * k), float(cond_scale), io, seed, node_base + n0,
                                 graph_base + g0, _lib.stream_handle(dev)), "chm_sample_step_dt")
@@ -451,11 +480,16 @@ class Chemeleon(nn.Module):
             else:
                 nz = (None, None, None, None)
             io = _lib.step_io(a, x, lat, cond, null, nz)
-            _lib.check(L.chm_sample_step(batch.handle, sched, t, float(cond_scale), io, seed, node_base, graph_base,
-                                         stream), "chm_sample_step")
+            if con is not None:
+                _lib.check(L.chm_sample_step_con(batch.handle, sched, t, None, float(cond_scale), io, con, seed,
+                                                 node_base, graph_base, stream), "chm_sample_step_con")
+            else:
+                _lib.check(L.chm_sample_step(batch.handle, sched, t, float(cond_scale), io, seed, node_base,
+                                             graph_base, stream), "chm_sample_step")
             yield (t - 1,) + emit(a, x, lat)
 
-    def _replay_torch_noise(self, batch, sched, a, x, lat, cond, null, cond_scale, step_noise, T, t_stop, emit):
+    def _replay_torch_noise(self, batch, sched, a, x, lat, cond, null, cond_scale, step_noise, T, t_stop, emit,
+                            con=None, seed: int = 0, node_base: int = 0, graph_base: int = 0):
         """Parity-mode noise (the reference's CPU RNG stream, this shard's rows of it) under a captured
         reverse step, with no copy on the device's critical path.
 
@@ -465,7 +499,8 @@ class Chemeleon(nn.Module):
         set t & 1 while step t+1 replays, after waiting for the replay that last read that set (two steps
         earlier), so the compute stream never waits for a copy and the draw hides under the replays.
         Bit-identical to eager stepping (test_torch_noise_graph_matches_eager): the same draws reach the
-        same kernels."""
+        same kernels. With a constraint (`con`) the captured step is chm_sample_step_con: the step's noise still
+        comes from the pinned sets, the replacement's from Philox (seed, node_base, graph_base)."""
         dev = self.device
         L = _lib.load()
         d_t = torch.full((1,), T, dtype=torch.int32, device=dev)
@@ -477,6 +512,12 @@ class Chemeleon(nn.Module):
         with torch.cuda.stream(side):
             for k in range(2):
                 with torch.cuda.graph(graphs[k], stream=side):
+                    if con is not None:
+                        _lib.check(L.chm_sample_step_con(
+                            batch.handle, sched, 0, _lib.ptr(d_t), float(cond_scale),
+                            _lib.step_io(a, x, lat, cond, null, pin[k]), con, seed, node_base, graph_base,
+                            _lib.stream_handle(dev)), "chm_sample_step_con")
+                        continue
                     _lib.check(L.chm_sample_step_dt_noise(
                         batch.handle, sched, _lib.ptr(d_t), float(cond_scale),
                         _lib.step_io(a, x, lat, cond, null, pin[k]), _lib.stream_handle(dev)),
@@ -499,10 +540,17 @@ class Chemeleon(nn.Module):
     @torch.no_grad()
     def reverse_step(self, t: int, atom_types, frac_coords, lattices, natoms: List[int], cond_scale: float = 2.0,
                      step_lr: float = 1e-5, text_embeds=None, null_text_embeds=None, noise=None, seed: int = 0,
-                     node_base: int = 0, graph_base: int = 0):
+                     node_base: int = 0, graph_base: int = 0, constraint=None, constraint_noise=None):
         """One step t -> t-1 (chemeleon.py:379-466) from an explicit state.
         `noise` = (rand_a, rand_l, rand_x1, rand_x2) tensors or None (Philox).
+        `constraint` (chemeleon_amd.Constraint): its known entries are held at level t-1 (see sample_states);
+        `constraint_noise` = (rand_a [N,A], rand_l [B,3,3], rand_x [N,3]) tensors for the replacement, or None
+        (Philox streams 4-6 of `seed`).
         Returns new (atom_types, frac_coords, lattices) device tensors."""
+        if constraint is None and constraint_noise is not None:
+            raise ValueError("constraint_noise needs a constraint")
+        if constraint is not None:
+            constraint.check_batch(natoms, self.max_atoms)
         dev = self.device
         natoms = [int(n) for n in natoms]
         a = atom_types.to(dev).long().clone().contiguous()
@@ -520,6 +568,13 @@ class Chemeleon(nn.Module):
         if noise is not None and [tuple(z.shape) for z in nz] != [(N, A), (B, 3, 3), (N, 3), (N, 3)]:
             raise ValueError(f"noise must be (rand_a [N,{A}], rand_l [B,3,3], rand_x1 [N,3], rand_x2 [N,3])")
         _lib.require_device(a, x, lat, cond, null, *nz)
+        if constraint is not None:
+            con, _con_keep = self._constraint_args(constraint, natoms, constraint_noise)
+            _lib.check(_lib.load().chm_sample_step_con(batch.handle, sched, int(t), None, float(cond_scale),
+                                                       _lib.step_io(a, x, lat, cond, null, nz), con, seed, node_base,
+                                                       graph_base, _lib.stream_handle(dev)),
+                       "chm_sample_step_con")
+            return a, x, lat
         _lib.check(_lib.load().chm_sample_step(batch.handle, sched, int(t), float(cond_scale),
                                                _lib.step_io(a, x, lat, cond, null, nz), seed, node_base, graph_base,
                                                _lib.stream_handle(dev)),

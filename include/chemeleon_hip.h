@@ -294,6 +294,75 @@ int chm_sample_step_dt(chm_batch* b, const chm_schedule* sched, int32_t* d_t, fl
 int chm_sample_step_dt_noise(chm_batch* b, const chm_schedule* sched, int32_t* d_t, float cond_scale,
                              const chm_step_io* io, void* stream);
 
+/* Constrained sampling (RePaint-style conditioning of the reverse loop; the reference has no counterpart: its
+ * composition workflow samples freely and discards what does not match, scripts/sample_target_composition.py:57-62).
+ * The caller marks atom types (per atom), fractional coordinates (per atom) and lattices (per crystal) as known.
+ * After a reverse step t -> t-1 has reached level s = t - 1, the marked entries are replaced by the known clean
+ * values forward-noised to level s, the q_sample of the training forward (chemeleon.py:151-180):
+ *   types        a = a0 at s = 0, else argmax_d(log(q_mats[s-1][a0][d] + 1e-6) - log(-log(clamp(u[i,d], 1e-6, 1)))),
+ *                the first maximum (diff_utils.py:236-256 at time s);
+ *   lattices     l = (fwd[s][0] l0 + fwd[s][1] (z_l mask9)) mask9, mask9 = [[1,0,1],[1,1,1],[0,0,1]];
+ *   coordinates  x = (x0 + fwd[s][2] z_x) % 1.0;
+ * every product and sum rounded to fp32 in this order. All buffers are in node order of the batch, each with its
+ * ELEMENT count (checked against the batch's N nodes, B crystals, A classes like chm_step_io's):
+ *   d_a0 [N] int64 + d_type_mask [N] uint8 (non-zero = known), d_x0 [N,3] + d_frac_mask [N] uint8,
+ *   d_l0 [B,3,3] (the model's lattice representation) + d_lattice_mask [B] uint8: each pair both given or both NULL
+ *     (NULL: nothing of that field is held);
+ *   d_fwd [T+1][4] = {sqrt(abar_t), sqrt(1 - abar_t), sigma_t, sigmas_norm_t} (chm_train_tables' d_coef4), n_fwd =
+ *     4 (T + 1) for the schedule's T;
+ *   the replacement's noise, all three or none: d_rand_a [N,A] uniforms, d_rand_l [B,3,3] normals (unmasked),
+ *     d_rand_x [N,3] normals. NULL: device Philox streams of kinds 4 (types, index (node_base + i) * 128 + class),
+ *     5 (lattices, (graph_base + g) * 9 + q) and 6 (coordinates, (node_base + i) * 3 + k), keyed by (seed, t) with
+ *     t = s + 1, the step's t. */
+typedef struct chm_constraint {
+  const int64_t* d_a0;
+  int64_t n_a0;
+  const uint8_t* d_type_mask;
+  int64_t n_type_mask;
+  const float* d_x0;
+  int64_t n_x0;
+  const uint8_t* d_frac_mask;
+  int64_t n_frac_mask;
+  const float* d_l0;
+  int64_t n_l0;
+  const uint8_t* d_lattice_mask;
+  int64_t n_lattice_mask;
+  const float* d_fwd;
+  int64_t n_fwd;
+  const float* d_rand_a;
+  int64_t n_rand_a;
+  const float* d_rand_l;
+  int64_t n_rand_l;
+  const float* d_rand_x;
+  int64_t n_rand_x;
+} chm_constraint;
+
+/* The replacement alone, in place on the state buffers of `io` (d_atom_types, d_frac, d_lattices; the other
+ * fields of io are not read). `level` = s is used when d_t is NULL; otherwise s = *d_t - 1 is read on the device
+ * (int32, the step's t). `what` selects the fields: bit 0 (1) types, bit 1 (2) lattices, bit 2 (4) coordinates.
+ * sched supplies T, num_classes and d_q_mats. Allocates nothing and does not synchronise: legal under stream
+ * capture. Every check (element counts, the pair and noise all-or-none rules, n_fwd against sched->T, level in
+ * [0, T], what in [1, 7]) returns CHM_E_ARG naming the field before the first HIP call. */
+int chm_constrain_state(chm_batch* b, const chm_schedule* sched, const chm_constraint* con, int level,
+                        const int32_t* d_t, int what, const chm_step_io* io, uint64_t seed, int64_t node_base,
+                        int64_t graph_base, void* stream);
+
+/* chm_sample_step with a constraint (con == NULL is refused: the three entry points above are the unconstrained
+ * step, unchanged). Host t is used when d_t is NULL; otherwise t is read from *d_t and decremented by the step's
+ * last kernel (graph replay). The step's own noise comes from io's four buffers when given, else from Philox.
+ * Order inside the step:
+ *   1. predictor decoder pair, predictor updates and D3PM sampling, as chm_sample_step;
+ *   2. stage 1: types, lattices and coordinates of the known entries replaced at level t - 1 (what = 7);
+ *   3. corrector decoder pair, which therefore sees the known atoms where they belong at that level;
+ *   4. Langevin corrector, as chm_sample_step;
+ *   5. stage 2: the known coordinates written again with the same noise (what = 4), so the corrector's move on
+ *      them is discarded; the free atoms keep theirs;
+ *   6. decrement of *d_t.
+ * A step whose constraint holds nothing of a stage's fields launches nothing for that stage. */
+int chm_sample_step_con(chm_batch* b, const chm_schedule* sched, int t, int32_t* d_t, float cond_scale,
+                        const chm_step_io* io, const chm_constraint* con, uint64_t seed, int64_t node_base,
+                        int64_t graph_base, void* stream);
+
 /* Standalone message-passing aggregation (scatter_mean of edge messages onto
  * their source node; chemeleon/utils/scatter.py:88-112 as called from
  * cspnet.py:155-160) over this batch's fc edge layout:
@@ -324,7 +393,8 @@ int chm_d3pm_sample(int N, int A, int T, const float* d_logits, const int64_t* d
  * from; the reference draws torch.rand / torch.randn on its CPU generator instead,
  * chemeleon.py:400-404,418,435,455):
  *   chm_debug_philox: d_out[i] = uniform in [0,1) (normal = 0) or standard normal (normal = 1)
- *     of key (seed, t, kind, base + i); kind 0 atom-type uniforms, 1 lattice, 2 / 3 coordinates.
+ *     of key (seed, t, kind, base + i); kind 0 atom-type uniforms, 1 lattice, 2 / 3 coordinates; 4 / 5 / 6 the
+ *     constraint's atom-type uniforms, lattice and coordinate normals (chm_constraint).
  *   chm_debug_d3pm_philox: chm_d3pm_sample with the Gumbel noise drawn from that stream (kind 0,
  *     index (node_base + node) * 128 + class), as the sampler does in perf mode. */
 int chm_debug_philox(uint64_t seed, int t, int kind, int64_t base, int64_t n, int normal, float* d_out, void* stream);
