@@ -8,6 +8,7 @@ reverse-diffusion sampling path, a drop-in for `chemeleon.Chemeleon` /
 from chemeleon_amd.modules.chemeleon import Chemeleon  # noqa: F401
 from chemeleon_amd.modules.cspnet import CSPNet, DECODER_OUTPUTS  # noqa: F401
 from chemeleon_amd.constraints import Constraint  # noqa: F401
+from chemeleon_amd.screening import Screen, ScreenReport, screen_states  # noqa: F401
 
-__all__ = ["Chemeleon", "CSPNet", "DECODER_OUTPUTS", "Constraint"]
+__all__ = ["Chemeleon", "CSPNet", "DECODER_OUTPUTS", "Constraint", "Screen", "ScreenReport", "screen_states"]
 __version__ = "0.1.0"

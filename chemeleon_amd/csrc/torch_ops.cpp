@@ -328,6 +328,70 @@ at::Tensor d3pm_sample(const at::Tensor& logits, const at::Tensor& xt, const at:
   return out;
 }
 
+// The screen of finished structures (chm_screen_run): cell parameters, the shortest periodic distance, formula
+// units and flags per crystal -> (floats [B,8] = a, b, c, alpha, beta, gamma, volume, dmin; ints [B,4] = i_min,
+// j_min, formula_units, flags). target: the wanted reduced element counts, int32 [104] or [B,104], or None.
+// Plans (node offsets on the device) are cached per (natoms, device), the last 8; the cache lives as long as
+// the process (nothing is freed during static destruction, when the HIP runtime may be gone).
+struct ScreenPlans {
+  std::mutex mu;
+  std::vector<std::tuple<std::vector<int64_t>, int, chm_screen*>> plans;
+  chm_screen* get(const std::vector<int64_t>& natoms, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
+    std::vector<int32_t> nat;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "screen: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    chm_screen* p = nullptr;
+    check(chm_screen_create(nat.data(), (int)nat.size(), &p), "chm_screen_create");
+    if (plans.size() >= 8) {
+      chm_screen_destroy(std::get<2>(plans.front()));
+      plans.erase(plans.begin());
+    }
+    plans.emplace_back(natoms, device, p);
+    return p;
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor> screen(const at::Tensor& atom_types, const at::Tensor& frac,
+                                          const at::Tensor& lattices, std::vector<int64_t> natoms,
+                                          const c10::optional<at::Tensor>& target, double max_length,
+                                          double min_distance) {
+  static ScreenPlans* cache = new ScreenPlans;
+  TORCH_CHECK(!natoms.empty(), "screen: natoms is empty");
+  const c10::Device dev = frac.device();
+  need_on(atom_types, dev, at::kLong, "atom_types");
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  need_shape(atom_types, {N}, "atom_types");
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  const int32_t* tg = nullptr;
+  int64_t n_tg = 0;
+  if (target.has_value()) {
+    need_on(*target, dev, at::kInt, "target");
+    TORCH_CHECK((target->dim() == 1 && target->size(0) == 104) ||
+                    (target->dim() == 2 && target->size(0) == B && target->size(1) == 104),
+                "target: expected shape [104] or [", B, ", 104], got ", target->sizes());
+    tg = target->data_ptr<int32_t>();
+    n_tg = target->numel();
+  }
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  chm_screen* plan = cache->get(natoms, dev.index());
+  at::Tensor rec = at::empty({B, 64}, at::TensorOptions().dtype(at::kByte).device(dev));
+  check(chm_screen_run(plan, atom_types.data_ptr<int64_t>(), atom_types.numel(), frac.data_ptr<float>(), frac.numel(),
+                       lattices.data_ptr<float>(), lattices.numel(), tg, n_tg, (float)max_length, (float)min_distance,
+                       rec.data_ptr(), (size_t)rec.numel(), stream()),
+        "chm_screen_run");
+  return {rec.view(at::kFloat).slice(1, 0, 8).contiguous(), rec.view(at::kInt).slice(1, 8, 12).contiguous()};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -352,6 +416,8 @@ TORCH_LIBRARY(chemeleon, m) {
         "int graph_base) -> ()");
   m.def("segment_mean(__torch__.torch.classes.chemeleon.Batch batch, int pairs, Tensor msg) -> Tensor");
   m.def("d3pm_sample(Tensor logits, Tensor x_t, Tensor t, Tensor noise, Tensor q_one_step, Tensor q_mats) -> Tensor");
+  m.def("screen(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? target, float max_length, "
+        "float min_distance) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -359,4 +425,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("sample_step", sample_step);
   m.impl("segment_mean", segment_mean);
   m.impl("d3pm_sample", d3pm_sample);
+  m.impl("screen", screen);
 }

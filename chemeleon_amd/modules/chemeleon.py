@@ -56,6 +56,8 @@ PATH_CHEMELEON_COMPOSITION = os.path.join(CHECKPOINT_DIR, "chemeleon-fksq6cgp.ck
 
 
 class Chemeleon(nn.Module):
+    last_screen = None  # the ScreenReport of the last sample(..., screen=...) call
+
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
         cfg = default_config()
@@ -645,7 +647,7 @@ class Chemeleon(nn.Module):
 
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
-               group=None, overlap: bool = True, **kw):
+               group=None, overlap: bool = True, screen=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -664,8 +666,22 @@ class Chemeleon(nn.Module):
 
         stream / return_trajectory convert every step to structures; overlap=True (default) does that one
         step behind the sampler from a device-side snapshot, overlap=False with the blocking step_to_atoms
-        (see _sample_generator). The results are identical."""
+        (see _sample_generator). The results are identical.
+
+        screen=Screen(...) (chemeleon_amd.screening): the final state is screened on the device (longest cell
+        edge, shortest periodic distance, reduced formula) and only the structures that pass are copied,
+        converted and returned, each with atoms.info["screen"]; the whole batch's report is kept as
+        self.last_screen. The screen is for finished structures: with stream / return_trajectory it raises
+        ValueError. Under multi-rank sampling every rank screens the gathered final state, so all ranks
+        return the same list. The keyword is not forwarded to sample_states."""
         natoms = [n_atoms] * n_samples
+        if screen is not None:
+            from chemeleon_amd.screening import Screen, screened_atoms
+            if not isinstance(screen, Screen):
+                raise ValueError("screen must be a chemeleon_amd.Screen")
+            if stream or return_trajectory:
+                raise ValueError("screen= applies to finished structures: not with stream / return_trajectory")
+            screen.target_for(n_samples)  # (a per-crystal formula list of the wrong length fails before sampling)
         texts = [text_input] * n_samples if text_input is not None else None
         kw.update(distributed=distributed, group=group)
         if stream:
@@ -682,6 +698,9 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
+        if screen is not None:
+            atoms, self.last_screen = screened_atoms(natoms, a, x, lat, screen)
+            return atoms
         return step_to_atoms(a, x, lat, natoms)
 
     def trajectory_container(self, natoms, texts=None, cond_scale=2.0, step_lr=1e-5, **kw) -> TrajectoryContainer:

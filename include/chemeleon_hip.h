@@ -586,6 +586,59 @@ int chm_snapshot_run(const chm_snapshot* plan, const int64_t* d_atom_types, int6
                      int64_t n_frac, const float* d_lattices, int64_t n_lattices, void* d_slot, size_t slot_bytes,
                      void* stream);
 
+/* Screening of finished structures on the device: what the reference's scripts do on the host with pymatgen
+ * before anything else looks at a sample (test_valid, scripts/evaluate.py: the longest cell edge at most 60 A
+ * and the shortest interatomic distance under periodic boundaries at least 0.5 A; the composition filter of
+ * scripts/sample_target_composition.py: the reduced formula is the one asked for). One record per crystal:
+ *   a, b, c              lengths of lattice rows 0, 1, 2 (A)
+ *   alpha, beta, gamma   angles in degrees between rows 1-2, rows 0-2, rows 0-1 (90 where a row is zero)
+ *   volume               |det|
+ *   dmin                 the shortest distance (A) over atom pairs i < j and ALL lattice translations; +inf for
+ *                        a one-atom crystal
+ *   i_min, j_min         indices inside the crystal of a pair that attains dmin (-1, -1 for one atom); ties go
+ *                        to the smallest squared distance first, then the smallest i, then the smallest j
+ *   formula_units        gcd of the non-zero element counts
+ *   flags                CHM_SCREEN_* bits; the structure passes when flags == 0
+ * Classes are clamped as in the snapshot (outside [0, 103] -> 0), and class 0 (X) counts as an element of its
+ * own, so a crystal that still holds one never matches a target.
+ * dmin is exact for any cell, not only over the 27 neighbouring cells: a first pass over the fractional
+ * differences wrapped to [-0.5, 0.5] and their 27 images gives an upper bound d0; a closer image lies within
+ * |n_k| <= 0.5 + d0 / h_k of the wrapped difference (h_k = volume / |L_{k+1} x L_{k+2}|, the spacing of the
+ * lattice planes along axis k), and where that range exceeds 1 on some axis a second pass searches it, up to 4
+ * per axis. A crystal that needs more (or whose volume is not > 0) gets CHM_SCREEN_DEGENERATE and dmin holds
+ * the capped search's value. Arithmetic is fp32, every product and sum rounded on its own.
+ * One deliberate difference from the reference's np.min(dist_mat[dist_mat > 0]): exactly coincident atoms are
+ * not ignored, they give dmin = 0 and fail the screen.
+ * d_target: the wanted REDUCED element counts (gcd 1), int32: NULL with n_target = 0 (no composition check),
+ * [104] for every crystal, or [B*104] per crystal. The plan holds the crystals' node offsets on the current
+ * device; create refuses bad arguments (NULL pointers, num_graphs <= 0, a natoms entry <= 0) with CHM_E_ARG
+ * before the device is touched. The run takes every buffer with its element count (the records with their
+ * byte count, 64 per crystal, at a 16-byte aligned address); a mismatch, or a threshold that is not > 0,
+ * returns CHM_E_ARG naming the buffer and nothing is enqueued. It allocates nothing, clears nothing and does
+ * not synchronise: legal under stream capture. */
+#define CHM_SCREEN_TOO_LONG 1     /* the longest edge > max_length */
+#define CHM_SCREEN_TOO_CLOSE 2    /* dmin < min_distance */
+#define CHM_SCREEN_COMPOSITION 4  /* reduced counts != target (only with a target) */
+#define CHM_SCREEN_DEGENERATE 8   /* image range capped, or volume not > 0 */
+#define CHM_SCREEN_NONFINITE 16   /* a non-finite lattice entry or coordinate */
+typedef struct {
+  float a, b, c;
+  float alpha, beta, gamma;
+  float volume;
+  float dmin;
+  int32_t i_min, j_min;
+  int32_t formula_units;
+  int32_t flags;
+  int32_t reserved[4]; /* written as 0 */
+} chm_screen_record;   /* 64 bytes */
+typedef struct chm_screen chm_screen;
+int chm_screen_create(const int32_t* h_natoms, int num_graphs, chm_screen** out);
+void chm_screen_destroy(chm_screen* plan);
+int chm_screen_run(const chm_screen* plan, const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                   int64_t n_frac, const float* d_lattices, int64_t n_lattices, const int32_t* d_target,
+                   int64_t n_target, float max_length, float min_distance, void* d_out, size_t n_out_bytes,
+                   void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
