@@ -135,6 +135,9 @@ SIGNATURES = {
     "chm_debug_philox": (c_int, [c_u64, c_int, c_int, c_i64, c_i64, c_int, c_void_p, c_void_p]),
     "chm_debug_d3pm_philox": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64,
                                       c_i64, c_void_p, c_void_p]),
+    "chm_debug_step_update": (c_int, [c_void_p, ctypes.POINTER(chm_schedule), c_int, c_void_p, c_float,
+                                      ctypes.POINTER(chm_step_io), c_u64, c_i64, c_i64, c_void_p, c_i64, c_void_p,
+                                      c_i64, c_void_p, c_i64, c_int, c_void_p]),
     "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
     "chm_debug_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                      c_void_p, c_void_p, c_void_p]),

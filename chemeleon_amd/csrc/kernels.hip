@@ -1,9 +1,15 @@
 // Device kernels of the Chemeleon sampling path for MI355X (gfx950, CDNA4).
 //
 // Numerics: every product / sum is fp32 (v_mfma_f32_32x32x2_f32 is an exact
-// fp32 fma chain); the elementwise step updates use explicitly rounded
-// __fmul_rn / __fadd_rn so hipcc cannot contract them into FMAs that the
-// reference's separate ATen ops do not perform.
+// fp32 fma chain). The reverse step's update kernels (k_step_predictor,
+// k_step_corrector, k_d3pm's guidance mix and its posterior + Gumbel sum) and
+// rem1 round every product and sum on its own, as the reference's separate
+// ATen ops do: they use mul_rn / add_rn / sub_rn below, plain operators
+// compiled with contraction off. The toolchain's __fmul_rn / __fadd_rn are
+// NOT that: they are plain * and + compiled in its headers with contraction
+// allowed, so hipcc fuses a product and a sum made of them into one FMA. The
+// training kernels still use them and may differ from the reference by such
+// fusions (DESIGN.md "The reverse step's update kernels").
 #include "chm_internal.h"
 
 #include <math.h>
@@ -15,11 +21,26 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 
+// a * b, a + b, a - b rounded once each: the pragma holds for the one statement of each body and travels with
+// the instruction when the helper is inlined, so no caller can fuse two of them into an FMA
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 // torch.remainder(x, 1.0) for fp32: fmod, then shift negatives by +1
 // (can return exactly 1.0 for tiny negatives, as the reference does).
 __device__ __forceinline__ float rem1(float x) {
   float m = fmodf(x, 1.0f);
-  if (m != 0.0f && m < 0.0f) m = __fadd_rn(m, 1.0f);
+  if (m != 0.0f && m < 0.0f) m = add_rn(m, 1.0f);
   return m;
 }
 
@@ -650,8 +671,8 @@ __global__ __launch_bounds__(256) void k_d3pm(int N, int A, int T, const float* 
     float lg0 = ok0 ? L1[i * ld + d0] : -INFINITY;
     float lg1 = ok1 ? L1[i * ld + d1] : -INFINITY;
     if (L2) {
-      if (ok0) lg0 = __fadd_rn(__fmul_rn(w1, L2[i * ld + d0]), __fmul_rn(w2, lg0));
-      if (ok1) lg1 = __fadd_rn(__fmul_rn(w1, L2[i * ld + d1]), __fmul_rn(w2, lg1));
+      if (ok0) lg0 = add_rn(mul_rn(w1, L2[i * ld + d0]), mul_rn(w2, lg0));
+      if (ok1) lg1 = add_rn(mul_rn(w1, L2[i * ld + d1]), mul_rn(w2, lg1));
     }
     // softmax over the A classes
     const float mx = wave_max(fmaxf(lg0, lg1));
@@ -695,14 +716,14 @@ __global__ __launch_bounds__(256) void k_d3pm(int N, int A, int T, const float* 
       float u = noise ? noise[i * A + d0] : rng_uniform(seed, t, 0, (uint64_t)(i + node_base) * 128 + d0);
       u = fminf(fmaxf(u, eps), 1.0f);
       const float gmb = -logf(-logf(u));
-      v0 = __fadd_rn(post, __fmul_rn(gmb, nz));
+      v0 = add_rn(post, mul_rn(gmb, nz));
     }
     if (ok1) {
       float post = (t == 1) ? lg1 : __fadd_rn(logf(Q1[d1 * A + x] + eps), logf(f21 + eps));
       float u = noise ? noise[i * A + d1] : rng_uniform(seed, t, 0, (uint64_t)(i + node_base) * 128 + d1);
       u = fminf(fmaxf(u, eps), 1.0f);
       const float gmb = -logf(-logf(u));
-      v1 = __fadd_rn(post, __fmul_rn(gmb, nz));
+      v1 = add_rn(post, mul_rn(gmb, nz));
     }
     float bv = v0;
     int bi = ok0 ? d0 : 1 << 30;
@@ -748,11 +769,11 @@ __global__ void k_step_predictor(StepArgs a) {
     const long col = a.A + k;
     const float pc = a.HO[i * HEADS_N + col];
     const float pn = a.HO[(a.N + i) * HEADS_N + col];
-    const float px = __fadd_rn(__fmul_rn(a.cs_null, pn), __fmul_rn(a.cs_cond, pc));
+    const float px = add_rn(mul_rn(a.cs_null, pn), mul_rn(a.cs_cond, pc));
     float z = 0.f;
     if (a.t > 1) z = a.rx1 ? a.rx1[idx] : rng_normal(a.seed, a.t, 2, (uint64_t)(i + a.node_base) * 3 + k);
-    const float pxs = __fmul_rn(px, cf[5]);
-    const float xh = __fadd_rn(__fsub_rn(a.x[idx], __fmul_rn(cf[3], pxs)), __fmul_rn(cf[4], z));
+    const float pxs = mul_rn(px, cf[5]);
+    const float xh = add_rn(sub_rn(a.x[idx], mul_rn(cf[3], pxs)), mul_rn(cf[4], z));
     a.x[idx] = xh;
   } else if (idx < nx + (long)a.B * 9) {
     const long r = idx - nx;
@@ -760,12 +781,12 @@ __global__ void k_step_predictor(StepArgs a) {
     const int q = (int)(r - gph * 9);
     const float pc = a.LAT[r];
     const float pn = a.LAT[(long)a.B * 9 + r];
-    const float pl = __fadd_rn(__fmul_rn(a.cs_null, pn), __fmul_rn(a.cs_cond, pc));
+    const float pl = add_rn(mul_rn(a.cs_null, pn), mul_rn(a.cs_cond, pc));
     float z = 0.f;
     if (a.t > 1) z = a.rl ? a.rl[r] : rng_normal(a.seed, a.t, 1, (uint64_t)(gph + a.graph_base) * 9 + q);
-    const float zm = __fmul_rn(z, c_lat_mask[q]);
-    float v = __fadd_rn(__fmul_rn(cf[0], __fsub_rn(a.l[r], __fmul_rn(cf[1], pl))), __fmul_rn(cf[2], zm));
-    v = __fmul_rn(v, c_lat_mask[q]);
+    const float zm = mul_rn(z, c_lat_mask[q]);
+    float v = add_rn(mul_rn(cf[0], sub_rn(a.l[r], mul_rn(cf[1], pl))), mul_rn(cf[2], zm));
+    v = mul_rn(v, c_lat_mask[q]);
     if (a.t == a.T) v = v < -6.f ? -6.f : (v > 6.f ? 6.f : v);
     a.l[r] = v;
   }
@@ -781,11 +802,11 @@ __global__ void k_step_corrector(StepArgs a) {
   const long col = a.A + k;
   const float pc = a.HO[i * HEADS_N + col];
   const float pn = a.HO[(a.N + i) * HEADS_N + col];
-  const float px = __fadd_rn(__fmul_rn(a.cs_null, pn), __fmul_rn(a.cs_cond, pc));
+  const float px = add_rn(mul_rn(a.cs_null, pn), mul_rn(a.cs_cond, pc));
   float z = 0.f;
   if (a.t > 1) z = a.rx2 ? a.rx2[idx] : rng_normal(a.seed, a.t, 3, (uint64_t)(i + a.node_base) * 3 + k);
-  const float pxs = __fmul_rn(px, cf[5]);
-  const float xn = __fadd_rn(__fsub_rn(a.x[idx], __fmul_rn(cf[6], pxs)), __fmul_rn(cf[7], z));
+  const float pxs = mul_rn(px, cf[5]);
+  const float xn = add_rn(sub_rn(a.x[idx], mul_rn(cf[6], pxs)), mul_rn(cf[7], z));
   a.x[idx] = rem1(xn);
 }
 

@@ -1688,7 +1688,8 @@ extern "C" int chm_decoder_forward(chm_batch* b, int pairs, const int64_t* a, co
 }
 
 // the element counts of a step's buffers against the batch (N nodes, B crystals) and its model
-static int check_step_io(const chm_batch* b, const chm_step_io* io, bool noise_required, bool noise_allowed) {
+static int check_step_io(const chm_batch* b, const chm_step_io* io, bool noise_required, bool noise_allowed,
+                         bool text_required = true) {
   if (!io) return fail(CHM_E_ARG, "io is NULL");
   const long N = b->N, B = b->B, A = b->m->d.max_atoms, X = b->m->d.text_dim;
   auto want = [&](const void* p, int64_t n, long expect, const char* name) -> int {
@@ -1702,7 +1703,7 @@ static int check_step_io(const chm_batch* b, const chm_step_io* io, bool noise_r
   if ((rc = want(io->d_atom_types, io->n_atom_types, N, "atom_types [N]"))) return rc;
   if ((rc = want(io->d_frac, io->n_frac, 3 * N, "frac [N,3]"))) return rc;
   if ((rc = want(io->d_lattices, io->n_lattices, 9 * B, "lattices [B,3,3]"))) return rc;
-  if (X > 0) {
+  if (X > 0 && text_required) {
     if ((rc = want(io->d_cond, io->n_cond, B * X, "cond [B,text_dim]"))) return rc;
     if ((rc = want(io->d_null, io->n_null, B * X, "null [B,text_dim]"))) return rc;
   }
@@ -1771,6 +1772,23 @@ static ConstrainArgs constrain_args(const chm_batch* b, const chm_schedule* sc, 
   return c;
 }
 
+// The update kernels' arguments of one step on the batch's decoder outputs (HO, LAT), for sample_step and
+// chm_debug_step_update alike. The guidance weights are formed from the ABI's float cond_scale: the null weight
+// is 1 - (double)cond_scale rounded once, which is the reference's fp32(1 - cond_scale) of the Python double only
+// where cond_scale is itself a float (2.0, 1.0, 0.0; not 1.3: DESIGN.md "The reverse step's update kernels").
+static StepArgs step_args(const chm_batch* b, const chm_schedule* sc, int t, const int* d_t, float cond_scale,
+                          const chm_step_io* io, uint64_t seed, int64_t node_base, int64_t graph_base) {
+  StepArgs sa;
+  std::memset(&sa, 0, sizeof(sa));
+  sa.t = t; sa.d_t = d_t; sa.T = sc->T; sa.A = b->m->d.max_atoms; sa.N = b->N; sa.B = b->B;
+  sa.cs_null = (float)(1.0 - (double)cond_scale); sa.cs_cond = cond_scale;
+  sa.coef = sc->d_coef; sa.q_one_step = sc->d_q_one_step; sa.q_mats = sc->d_q_mats;
+  sa.HO = b->HO; sa.LAT = b->LAT; sa.a = io->d_atom_types; sa.x = io->d_frac; sa.l = io->d_lattices; sa.n2g = b->n2g;
+  if (io->d_rand_a) { sa.ra = io->d_rand_a; sa.rl = io->d_rand_l; sa.rx1 = io->d_rand_x1; sa.rx2 = io->d_rand_x2; }
+  sa.seed = seed; sa.node_base = node_base; sa.graph_base = graph_base;
+  return sa;
+}
+
 // con != null (chm_sample_step_con): the known entries are replaced at level t - 1 between the predictor and the
 // corrector's decoder call (stage 1) and the known coordinates again behind the corrector (stage 2, same noise)
 static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, float cond_scale, const chm_step_io* io,
@@ -1790,7 +1808,6 @@ static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, fl
   int rc = check_step_io(b, io, noise_required, noise_allowed);
   if (rc) return rc;
   if (con && (rc = check_constraint(b, sc, con))) return rc;
-  const bool host_noise = io->d_rand_a != nullptr;
   int64_t* d_a = io->d_atom_types;
   float *d_x = io->d_frac, *d_l = io->d_lattices;
   const float *d_cond = b->m->d.text_dim > 0 ? io->d_cond : nullptr, *d_null = b->m->d.text_dim > 0 ? io->d_null : nullptr;
@@ -1798,14 +1815,7 @@ static int sample_step(chm_batch* b, const chm_schedule* sc, int t, int* d_t, fl
   const float* temb = d_t ? sc->d_time_emb : sc->d_time_emb + (size_t)t * TD;
   rc = run_decoder(b, 2, d_a, d_x, d_l, temb, 0, d_t, d_cond, d_null, 3, s);
   if (rc) return rc;
-  StepArgs sa;
-  std::memset(&sa, 0, sizeof(sa));
-  sa.t = t; sa.d_t = d_t; sa.T = sc->T; sa.A = b->m->d.max_atoms; sa.N = b->N; sa.B = b->B;
-  sa.cs_null = (float)(1.0 - (double)cond_scale); sa.cs_cond = cond_scale;
-  sa.coef = sc->d_coef; sa.q_one_step = sc->d_q_one_step; sa.q_mats = sc->d_q_mats;
-  sa.HO = b->HO; sa.LAT = b->LAT; sa.a = d_a; sa.x = d_x; sa.l = d_l; sa.n2g = b->n2g;
-  if (host_noise) { sa.ra = io->d_rand_a; sa.rl = io->d_rand_l; sa.rx1 = io->d_rand_x1; sa.rx2 = io->d_rand_x2; }
-  sa.seed = seed; sa.node_base = node_base; sa.graph_base = graph_base;
+  const StepArgs sa = step_args(b, sc, t, d_t, cond_scale, io, seed, node_base, graph_base);
   HIPCHK(step_predictor(sa, s));
   ConstrainArgs ca;
   if (con) {  // stage 1: the corrector's decoder call sees the known entries at level t - 1
@@ -1846,6 +1856,57 @@ extern "C" int chm_sample_step_con(chm_batch* b, const chm_schedule* sc, int t, 
   if (!con) return fail(CHM_E_ARG, "constraint is NULL (chm_sample_step is the unconstrained step)");
   return sample_step(b, sc, d_t ? 0 : t, d_t, cond_scale, io, false, true, seed, node_base, graph_base,
                      (hipStream_t)stream, con);
+}
+
+// The update half of a step on caller-supplied decoder outputs (tests/test_gpu_step_update.py): step_predictor /
+// step_corrector with sample_step's StepArgs. Every argument check runs before the first HIP call.
+extern "C" int chm_debug_step_update(chm_batch* b, const chm_schedule* sc, int t, const int32_t* d_t, float cond_scale,
+                                     const chm_step_io* io, uint64_t seed, int64_t node_base, int64_t graph_base,
+                                     const float* d_types, int64_t n_types, const float* d_coords, int64_t n_coords,
+                                     const float* d_lattice, int64_t n_lattice, int stage, void* stream) {
+  auto bad = [&](const std::string& why) { return fail(CHM_E_ARG, "chm_debug_step_update: " + why); };
+  // what needs no batch first, so that those refusals can be tested without a device
+  if (!sc) return bad("schedule is NULL");
+  if (!io) return bad("io is NULL");
+  if (stage != 1 && stage != 2) return bad("stage " + std::to_string(stage) + " outside {1, 2}");
+  if (sc->T < 1) return bad("schedule: T must be >= 1");
+  if (!d_t && (t < 1 || t > sc->T))
+    return bad("t " + std::to_string(t) + " outside [1, " + std::to_string(sc->T) + "]");
+  if (!sc->d_coef || !sc->d_q_one_step || !sc->d_q_mats) return bad("NULL schedule table");
+  if (!io->d_atom_types || !io->d_frac || !io->d_lattices) return bad("io: a state buffer is NULL");
+  const int given = (io->d_rand_a != nullptr) + (io->d_rand_l != nullptr) + (io->d_rand_x1 != nullptr) +
+                    (io->d_rand_x2 != nullptr);
+  if (given != 0 && given != 4) return bad("noise: all four buffers or none");
+  if (!d_coords) return bad("d_coords is NULL");
+  if (stage == 1 && !d_types) return bad("d_types is NULL (stage 1)");
+  if (stage == 1 && !d_lattice) return bad("d_lattice is NULL (stage 1)");
+  if (!b) return bad("batch is NULL");
+  if (b->P < 2) return bad("max_pairs: the batch needs 2 (its head buffers hold the cond and the null outputs)");
+  if (sc->num_classes != b->m->d.max_atoms || sc->time_dim != b->m->d.time_dim)
+    return bad("schedule: num_classes " + std::to_string(sc->num_classes) + " / time_dim " +
+               std::to_string(sc->time_dim) + " do not match the model's " + std::to_string(b->m->d.max_atoms) +
+               " / " + std::to_string(b->m->d.time_dim));
+  int rc = check_step_io(b, io, false, true, false);
+  if (rc) return rc;
+  const long N = b->N, B = b->B, A = b->m->d.max_atoms;
+  auto sized = [&](const void* p, int64_t n, long expect, const char* name) -> int {
+    if (p && n != expect)
+      return bad(std::string(name) + ": " + std::to_string(n) + " elements, the batch needs " + std::to_string(expect));
+    return CHM_OK;
+  };
+  if ((rc = sized(d_types, n_types, 2 * N * A, "n_types [2,N,A]"))) return rc;
+  if ((rc = sized(d_coords, n_coords, 2 * N * 3, "n_coords [2,N,3]"))) return rc;
+  if ((rc = sized(d_lattice, n_lattice, 2 * B * 9, "n_lattice [2,B,3,3]"))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (d_types) HIPCHK(copy_rows(d_types, A, b->HO, HEADS_N, 2 * N, (int)A, s));
+  HIPCHK(copy_rows(d_coords, 3, b->HO + A, HEADS_N, 2 * N, 3, s));
+  if (d_lattice)
+    HIPCHK(hipMemcpyAsync(b->LAT, d_lattice, (size_t)2 * B * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const StepArgs sa = step_args(b, sc, t, d_t, cond_scale, io, seed, node_base, graph_base);
+  if (stage == 1) HIPCHK(step_predictor(sa, s));
+  else HIPCHK(step_corrector(sa, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return CHM_OK;
 }
 
 extern "C" int chm_constrain_state(chm_batch* b, const chm_schedule* sc, const chm_constraint* con, int level,

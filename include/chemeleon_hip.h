@@ -402,6 +402,27 @@ int chm_debug_d3pm_philox(int N, int A, int T, const float* d_logits, const int6
                           const float* d_q_one_step, const float* d_q_mats, uint64_t seed, int64_t node_base,
                           int64_t* d_out, void* stream);
 
+/* Test hook: the update half of a reverse step on caller-supplied decoder outputs, by the very code
+ * chm_sample_step runs behind its decoder calls (the same kernels, launched with arguments built by the same
+ * function). d_types [2,N,A], d_coords [2,N,3], d_lattice [2,B,3,3]: the conditional outputs first, then the
+ * null ones, as chm_decoder_forward with pairs = 2 returns them, each with its ELEMENT count; they are packed
+ * into the batch's own head buffers (the batch needs max_pairs = 2).
+ *   stage 1: the predictor: D3PM atom types (the two logit sets mixed by cond_scale, written in place over
+ *            io->d_atom_types), the DDPM lattice update with its clip at t == T, the VE predictor half step;
+ *   stage 2: the Langevin corrector and the wrap to [0, 1) on io->d_frac; d_types and d_lattice may be NULL.
+ * t is the host value when d_t is NULL, else *d_t (int32) is read on the device; it is not decremented. io: the
+ * state in place and the four noise buffers or none (then Philox streams 0-3 keyed by (seed, t): atom-type
+ * uniforms at (node_base + i) * 128 + class, lattice normals at (graph_base + g) * 9 + q, the predictor's and
+ * the corrector's coordinate normals at (node_base + i) * 3 + k); d_cond / d_null are not read. As in the step,
+ * a host t == 1 reads no noise; with d_t the atom-type uniforms are read at t == 1 too and must be finite.
+ * For tests only: it synchronises the stream. Every check (NULL pointers, element counts, max_pairs, stage in
+ * {1, 2}, host t in [1, T], the noise all-or-none rule, the schedule's num_classes / time_dim) returns
+ * CHM_E_ARG naming the field before the first HIP call, without a device. */
+int chm_debug_step_update(chm_batch* b, const chm_schedule* sched, int t, const int32_t* d_t, float cond_scale,
+                          const chm_step_io* io, uint64_t seed, int64_t node_base, int64_t graph_base,
+                          const float* d_types, int64_t n_types, const float* d_coords, int64_t n_coords,
+                          const float* d_lattice, int64_t n_lattice, int stage, void* stream);
+
 /* Test hook: one GEMM kernel of the decoder on caller-supplied fp32 device operands,
  * C[M,N] = epi(A[M,K] . W[N,K]^T), the weights packed exactly as chm_model_create packs them
  * (bf16 planes for kinds 1-3, row-scaled fp16 split rows in 16-column chunks for kind 4, in
