@@ -9,6 +9,9 @@ from chemeleon_amd.modules.chemeleon import Chemeleon  # noqa: F401
 from chemeleon_amd.modules.cspnet import CSPNet, DECODER_OUTPUTS  # noqa: F401
 from chemeleon_amd.constraints import Constraint  # noqa: F401
 from chemeleon_amd.screening import Screen, ScreenReport, screen_states  # noqa: F401
+from chemeleon_amd.dedup import (Dedup, DedupReport, Fingerprints, dedup_states, fingerprint_states,  # noqa: F401
+                                 group_fingerprints)
 
-__all__ = ["Chemeleon", "CSPNet", "DECODER_OUTPUTS", "Constraint", "Screen", "ScreenReport", "screen_states"]
+__all__ = ["Chemeleon", "CSPNet", "DECODER_OUTPUTS", "Constraint", "Screen", "ScreenReport", "screen_states",
+           "Dedup", "DedupReport", "Fingerprints", "dedup_states", "fingerprint_states", "group_fingerprints"]
 __version__ = "0.1.0"

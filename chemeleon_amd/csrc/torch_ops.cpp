@@ -392,6 +392,78 @@ std::tuple<at::Tensor, at::Tensor> screen(const at::Tensor& atom_types, const at
   return {rec.view(at::kFloat).slice(1, 0, 8).contiguous(), rec.view(at::kInt).slice(1, 8, 12).contiguous()};
 }
 
+// Grouping of duplicate structures (chm_dedup_fingerprint + chm_dedup_group): the state's fingerprints
+// ([B, 2 * bins], include/chemeleon_hip.h) and their groups by the leader rule -> (group [B] int32: the
+// representative's index or -1, count [B] int32: the group's size at a representative, fingerprint). exclude: a
+// bool / uint8 tensor [B] of crystals that take no part, or None. Plans are cached as the screen's.
+struct DedupPlans {
+  std::mutex mu;
+  std::vector<std::tuple<std::vector<int64_t>, int, chm_dedup*>> plans;
+  chm_dedup* get(const std::vector<int64_t>& natoms, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
+    std::vector<int32_t> nat;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "dedup: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    chm_dedup* p = nullptr;
+    check(chm_dedup_create(nat.data(), (int)nat.size(), &p), "chm_dedup_create");
+    if (plans.size() >= 8) {
+      chm_dedup_destroy(std::get<2>(plans.front()));
+      plans.erase(plans.begin());
+    }
+    plans.emplace_back(natoms, device, p);
+    return p;
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> dedup(const at::Tensor& atom_types, const at::Tensor& frac,
+                                                     const at::Tensor& lattices, std::vector<int64_t> natoms,
+                                                     const c10::optional<at::Tensor>& exclude, double tol,
+                                                     double r_cut, double sigma, int64_t bins) {
+  static DedupPlans* cache = new DedupPlans;
+  TORCH_CHECK(!natoms.empty(), "dedup: natoms is empty");
+  TORCH_CHECK(bins >= 8 && bins <= 256, "dedup: bins must be in [8, 256], got ", bins);
+  const c10::Device dev = frac.device();
+  need_on(atom_types, dev, at::kLong, "atom_types");
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  need_shape(atom_types, {N}, "atom_types");
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  const uint8_t* ex = nullptr;
+  if (exclude.has_value()) {
+    TORCH_CHECK(exclude->scalar_type() == at::kBool || exclude->scalar_type() == at::kByte,
+                "exclude: expected bool or uint8, got ", exclude->scalar_type());
+    need_on(*exclude, dev, exclude->scalar_type(), "exclude");
+    need_shape(*exclude, {B}, "exclude");
+    ex = static_cast<const uint8_t*>(exclude->data_ptr());
+  }
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  chm_dedup* plan = cache->get(natoms, dev.index());
+  const auto ints = at::TensorOptions().dtype(at::kInt).device(dev);
+  at::Tensor fp = at::empty({B, 2 * bins}, frac.options()), counts = at::empty({B, 104}, ints),
+             flags = at::empty({B}, ints), group = at::empty({B}, ints), count = at::empty({B}, ints);
+  const size_t ws_bytes = chm_dedup_workspace_bytes(B);
+  at::Tensor ws = at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+  check(chm_dedup_fingerprint(plan, atom_types.data_ptr<int64_t>(), atom_types.numel(), frac.data_ptr<float>(),
+                              frac.numel(), lattices.data_ptr<float>(), lattices.numel(), (int)bins, (float)r_cut,
+                              (float)sigma, fp.data_ptr<float>(), fp.numel(), counts.data_ptr<int32_t>(),
+                              counts.numel(), flags.data_ptr<int32_t>(), flags.numel(), stream()),
+        "chm_dedup_fingerprint");
+  check(chm_dedup_group(B, (int)bins, fp.data_ptr<float>(), fp.numel(), counts.data_ptr<int32_t>(), counts.numel(),
+                        flags.data_ptr<int32_t>(), flags.numel(), ex, ex ? B : 0, (float)tol,
+                        group.data_ptr<int32_t>(), group.numel(), count.data_ptr<int32_t>(), count.numel(),
+                        ws.data_ptr(), ws_bytes, stream()),
+        "chm_dedup_group");
+  return {group, count, fp};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -418,6 +490,8 @@ TORCH_LIBRARY(chemeleon, m) {
   m.def("d3pm_sample(Tensor logits, Tensor x_t, Tensor t, Tensor noise, Tensor q_one_step, Tensor q_mats) -> Tensor");
   m.def("screen(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? target, float max_length, "
         "float min_distance) -> (Tensor, Tensor)");
+  m.def("dedup(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? exclude, float tol, "
+        "float r_cut, float sigma, int bins) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -426,4 +500,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("segment_mean", segment_mean);
   m.impl("d3pm_sample", d3pm_sample);
   m.impl("screen", screen);
+  m.impl("dedup", dedup);
 }

@@ -57,6 +57,7 @@ PATH_CHEMELEON_COMPOSITION = os.path.join(CHECKPOINT_DIR, "chemeleon-fksq6cgp.ck
 
 class Chemeleon(nn.Module):
     last_screen = None  # the ScreenReport of the last sample(..., screen=...) call
+    last_dedup = None   # the DedupReport of the last sample(..., dedup=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
@@ -647,7 +648,7 @@ class Chemeleon(nn.Module):
 
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
-               group=None, overlap: bool = True, screen=None, **kw):
+               group=None, overlap: bool = True, screen=None, dedup=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -673,8 +674,22 @@ class Chemeleon(nn.Module):
         converted and returned, each with atoms.info["screen"]; the whole batch's report is kept as
         self.last_screen. The screen is for finished structures: with stream / return_trajectory it raises
         ValueError. Under multi-rank sampling every rank screens the gathered final state, so all ranks
-        return the same list. The keyword is not forwarded to sample_states."""
+        return the same list. The keyword is not forwarded to sample_states.
+
+        dedup=Dedup(...) (chemeleon_amd.dedup): the final state is grouped on the device (equal reduced formulas
+        and fingerprints within tol, the leader rule of group_structures) and only one representative per group
+        is copied, converted and returned, each with atoms.info["dedup"] = {"index", "group", "multiplicity"};
+        the whole report is kept as self.last_dedup. With screen= as well the screen runs first and its failures
+        take no part: they are neither returned nor representatives. Like the screen it is for finished
+        structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
+        rank."""
         natoms = [n_atoms] * n_samples
+        if dedup is not None:
+            from chemeleon_amd.dedup import Dedup, deduped_atoms
+            if not isinstance(dedup, Dedup):
+                raise ValueError("dedup must be a chemeleon_amd.Dedup")
+            if stream or return_trajectory:
+                raise ValueError("dedup= applies to finished structures: not with stream / return_trajectory")
         if screen is not None:
             from chemeleon_amd.screening import Screen, screened_atoms
             if not isinstance(screen, Screen):
@@ -698,6 +713,11 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
+        if dedup is not None:
+            atoms, self.last_dedup, screened = deduped_atoms(natoms, a, x, lat, dedup, screen)
+            if screen is not None:
+                self.last_screen = screened
+            return atoms
         if screen is not None:
             atoms, self.last_screen = screened_atoms(natoms, a, x, lat, screen)
             return atoms

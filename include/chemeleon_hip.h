@@ -660,6 +660,66 @@ int chm_screen_run(const chm_screen* plan, const int64_t* d_atom_types, int64_t 
                    int64_t n_target, float max_length, float min_distance, void* d_out, size_t n_out_bytes,
                    void* stream);
 
+/* Grouping of duplicate structures on the device: the third leg of the reference's sample -> validity ->
+ * uniqueness workflows (test_unique of scripts/evaluate.py and the grouping of
+ * scripts/navigate_chemical_system.py, both StructureMatcher().group_structures on the host). This is NOT a port
+ * of pymatgen's StructureMatcher: two crystals are duplicates when their reduced element counts are equal and
+ * their fingerprints are close; how that criterion agrees with the matcher has not been measured.
+ *
+ * The fingerprint of a crystal with n atoms, classes z_i (clamped as in the screen: outside [0, 103] -> 0),
+ * fractional coordinates x_i and lattice L (rows are vectors, Cartesian = frac . L) is a smooth radial
+ * distribution per atom in C = 2 channels of K bins, bin centres r_k = (k + 0.5) r_cut / K:
+ *   F[c][k] = (1/n) sum_i sum_j sum_R  w_c(i,j) exp(-(d - r_k)^2 / (2 sigma^2)) (1/2)(1 + cos(pi d / r_cut))
+ *             over every lattice translation R with d = |(x_j - x_i + R) L| <= r_cut, except (i = j, R = 0),
+ *             and only into the bins with |d - r_k| <= 6 sigma
+ *   w_0 = 1,  w_1 = z_i z_j / zbar^2,  zbar = the crystal's mean class (zbar = 0: channel 1 is all zeros)
+ * stored as fp[2K] = channel 0's K bins, then channel 1's. The support of 6 sigma is part of the definition: a
+ * dropped term is below exp(-18) = 1.5e-8 of the pair's weight, while the same pair adds at least 0.95 of its
+ * weight to its nearest bin at the defaults (K = 64, r_cut = 6.0, sigma = 0.15: the nearest centre is within
+ * 0.31 sigma), so what is dropped is less than half an fp32 ulp (2^-24 = 6.0e-8) of what is kept. The taper makes F
+ * continuous in the coordinates (a pair that crosses r_cut contributes nothing there). F is intensive and
+ * invariant under atom permutation, a common translation, rotation, any unimodular change of the lattice basis
+ * and the choice of supercell: the same crystal written with 6 or with 12 atoms has the same fingerprint.
+ * Images: the difference x_j - x_i is wrapped to [-0.5, 0.5] and the translations |R_k| <= 0.5 + r_cut / h_k
+ * (widened by 1e-5; h_k = volume / |L_{k+1} x L_{k+2}| as in the screen) are searched, at most 8 per axis. A
+ * crystal that needs more, or whose volume is not > 0, gets CHM_DEDUP_DEGENERATE; one with a non-finite lattice
+ * entry or coordinate CHM_DEDUP_NONFINITE. A flagged crystal's fingerprint is all zeros and it is never grouped.
+ * Arithmetic is fp32 with accurate expf / cosf / sqrtf, every product and sum rounded on its own (no
+ * contraction): d as in the screen, t = d - r_k, term = (expf(-(t t) / (2 sigma^2)) taper) [z_i z_j], summed
+ * per bin in a fixed order that depends on the crystal alone (no float atomics), then channel 0 divided by n
+ * and channel 1 multiplied by n / (sum_i z_i)^2. Two runs, and a crystal alone or inside any batch, give the
+ * same bits. counts[104] are the crystal's element counts divided by their gcd (the screen's formula
+ * reduction); compositions are compared by integer equality only.
+ *
+ * Grouping takes free-standing fingerprints ([B, 2K], with counts [B,104] and optionally flags [B] and an
+ * exclusion mask of B bytes), so the union of several fingerprint calls (several cell sizes) groups as one
+ * list. Crystals g < h match when neither is flagged or excluded, their counts are equal and
+ *   |F_g - F_h|^2 <= tol^2 max(|F_g|^2, |F_h|^2)         (fp32, each sum over the 2K entries in order)
+ * and groups follow the leader rule of group_structures: in index order, g is a representative when it matches
+ * no earlier representative, otherwise it joins the earliest representative it matches (not transitive, on
+ * purpose). group[g] is the representative's index (g itself for a representative), or -1 for a flagged or
+ * excluded crystal; count[g] is the group's size at a representative, 0 elsewhere.
+ * The plan holds the crystals' node offsets on the current device (create: as the screen's). Both run calls
+ * take every buffer with its element count (the workspace with its byte count, at a 4-byte aligned address);
+ * NULL pointers, B <= 0, K outside [8, 256], an r_cut, sigma or tol that is not positive and finite, a
+ * mismatched count or a short workspace return CHM_E_ARG naming the argument before the first HIP call, and
+ * nothing is enqueued. They allocate nothing and do not synchronise: legal under stream capture.
+ * d_flags (n_flags = 0 or B) and d_exclude (n_exclude = 0 or B) may be NULL with a count of 0. */
+#define CHM_DEDUP_DEGENERATE 8   /* image range capped, or volume not > 0 */
+#define CHM_DEDUP_NONFINITE 16   /* a non-finite lattice entry or coordinate */
+typedef struct chm_dedup chm_dedup;
+int chm_dedup_create(const int32_t* h_natoms, int num_graphs, chm_dedup** out);
+void chm_dedup_destroy(chm_dedup* plan);
+int chm_dedup_fingerprint(const chm_dedup* plan, const int64_t* d_atom_types, int64_t n_atom_types,
+                          const float* d_frac, int64_t n_frac, const float* d_lattices, int64_t n_lattices, int K,
+                          float r_cut, float sigma, float* d_fp, int64_t n_fp, int32_t* d_counts, int64_t n_counts,
+                          int32_t* d_flags, int64_t n_flags, void* stream);
+size_t chm_dedup_workspace_bytes(int64_t B);
+int chm_dedup_group(int64_t B, int K, const float* d_fp, int64_t n_fp, const int32_t* d_counts, int64_t n_counts,
+                    const int32_t* d_flags, int64_t n_flags, const uint8_t* d_exclude, int64_t n_exclude, float tol,
+                    int32_t* d_group, int64_t n_group, int32_t* d_count, int64_t n_count, void* d_workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
