@@ -138,6 +138,8 @@ SIGNATURES = {
     "chm_debug_step_update": (c_int, [c_void_p, ctypes.POINTER(chm_schedule), c_int, c_void_p, c_float,
                                       ctypes.POINTER(chm_step_io), c_u64, c_i64, c_i64, c_void_p, c_i64, c_void_p,
                                       c_i64, c_void_p, c_i64, c_int, c_void_p]),
+    "chm_debug_train_update": (c_int, [c_void_p, ctypes.POINTER(chm_train_tables)] + [c_void_p] * 8 +
+                               [c_i64, c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 7),
     "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
     "chm_debug_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                      c_void_p, c_void_p, c_void_p]),

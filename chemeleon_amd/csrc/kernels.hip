@@ -8,8 +8,10 @@
 // compiled with contraction off. The toolchain's __fmul_rn / __fadd_rn are
 // NOT that: they are plain * and + compiled in its headers with contraction
 // allowed, so hipcc fuses a product and a sum made of them into one FMA. The
-// training kernels still use them and may differ from the reference by such
-// fusions (DESIGN.md "The reverse step's update kernels").
+// training forward's q_sample (k_train_noise, k_train_lattice, dlogp_wrapped)
+// uses mul_rn / add_rn too; k_train_node_loss keeps its fmaf chain over the
+// classes (the documented summation) and its losses are held against float64
+// within a tolerance (DESIGN.md "The training kernels").
 #include "chm_internal.h"
 
 #include <math.h>
@@ -832,13 +834,13 @@ hipError_t step_corrector(const StepArgs& a, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // d_log_p_wrapped_normal(x, sigma) (diff_utils.py:35-47): 21 wrapped terms, the reference's order
 __device__ __forceinline__ float dlogp_wrapped(float x, float s) {
-  const float s2 = __fmul_rn(s, s);
+  const float s2 = mul_rn(s, s);
   float num = 0.f, den = 0.f;
   for (int i = -10; i <= 10; ++i) {
-    const float u = __fadd_rn(x, (float)i);
-    const float e = expf(__fdiv_rn(__fdiv_rn(-__fmul_rn(u, u), 2.0f), s2));
-    num = __fadd_rn(num, __fmul_rn(__fdiv_rn(u, s2), e));
-    den = __fadd_rn(den, e);
+    const float u = add_rn(x, (float)i);
+    const float e = expf(__fdiv_rn(__fdiv_rn(-mul_rn(u, u), 2.0f), s2));
+    num = add_rn(num, mul_rn(__fdiv_rn(u, s2), e));
+    den = add_rn(den, e);
   }
   return __fdiv_rn(num, den);
 }
@@ -857,9 +859,9 @@ __global__ __launch_bounds__(256) void k_train_noise(TrainArgs g) {
   float bv = -INFINITY;
   int bi = 0;
   for (int d = lane; d < A; d += 64) {
-    const float lg = logf(__fadd_rn(Q[d], eps));
+    const float lg = logf(add_rn(Q[d], eps));
     const float u = fminf(fmaxf(g.rand_a[i * A + d], eps), 1.0f);
-    const float v = __fadd_rn(lg, -logf(-logf(u)));
+    const float v = add_rn(lg, -logf(-logf(u)));
     if (better(v, d, bv, bi)) { bv = v; bi = d; }
   }
 #pragma unroll
@@ -871,8 +873,8 @@ __global__ __launch_bounds__(256) void k_train_noise(TrainArgs g) {
   if (lane == 0) g.a_t[i] = bi;
   if (lane < 3) {
     const float* cf = g.coef + (long)t * 4;  // {sqrt(abar), sqrt(1 - abar), sigma_x, sigma_norm}
-    const float sz = __fmul_rn(cf[2], g.noise_x[i * 3 + lane]);
-    g.x_t[i * 3 + lane] = rem1(__fadd_rn(g.x0[i * 3 + lane], sz));
+    const float sz = mul_rn(cf[2], g.noise_x[i * 3 + lane]);
+    g.x_t[i * 3 + lane] = rem1(add_rn(g.x0[i * 3 + lane], sz));
     g.target_x[i * 3 + lane] = __fdiv_rn(dlogp_wrapped(sz, cf[2]), sqrtf(cf[3]));
   }
 }
@@ -882,7 +884,7 @@ __global__ void k_train_lattice(TrainArgs g) {
   const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= (long)g.B * 9) return;
   const float* cf = g.coef + g.t[k / 9] * 4;
-  g.l_t[k] = __fadd_rn(__fmul_rn(cf[0], g.l0[k]), __fmul_rn(cf[1], g.noise_l[k]));
+  g.l_t[k] = add_rn(mul_rn(cf[0], g.l0[k]), mul_rn(cf[1], g.noise_l[k]));
 }
 
 // one wave per node: true and predicted posterior logits (q_posterior_logits, diff_utils.py:258-286),
@@ -898,19 +900,19 @@ __global__ __launch_bounds__(256) void k_train_node_loss(TrainArgs g) {
   const float eps = 1.0e-6f;
   const int x0 = (int)g.a0[i], xt = (int)g.a_t[i];
   const int d0 = lane, d1 = lane + 64;
-  const bool ok1 = d1 < A;
+  const bool ok0 = d0 < A, ok1 = d1 < A;  // (A < 64: the lanes d0 >= A hold no class, as in k_d3pm)
   const float* P = g.HO + i * HEADS_N;  // predicted x_0 logits (types head)
-  const float lg0 = P[d0], lg1 = ok1 ? P[d1] : -INFINITY;
+  const float lg0 = ok0 ? P[d0] : -INFINITY, lg1 = ok1 ? P[d1] : -INFINITY;
   // softmax of the prediction
   const float mx = wave_max(fmaxf(lg0, lg1));
-  const float e0 = expf(lg0 - mx), e1 = ok1 ? expf(lg1 - mx) : 0.f;
+  const float e0 = ok0 ? expf(lg0 - mx) : 0.f, e1 = ok1 ? expf(lg1 - mx) : 0.f;
   const float se = wave_sum(e0 + e1);
-  sm[d0] = e0 / se;
+  if (ok0) sm[d0] = e0 / se;
   if (ok1) sm[d1] = e1 / se;
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
   // true x_0 logits: log(one_hot + eps); its softmax row is (1 + eps, eps, ...) normalised
-  const float tl0 = logf(__fadd_rn(d0 == x0 ? 1.0f : 0.0f, eps));
+  const float tl0 = ok0 ? logf(__fadd_rn(d0 == x0 ? 1.0f : 0.0f, eps)) : -INFINITY;
   const float tl1 = ok1 ? logf(__fadd_rn(d1 == x0 ? 1.0f : 0.0f, eps)) : -INFINITY;
   float q0 = lg0, q1 = lg1, p0 = tl0, p1 = tl1;  // (t == 1: the x_0 logits themselves)
   if (t != 1) {
@@ -919,22 +921,26 @@ __global__ __launch_bounds__(256) void k_train_node_loss(TrainArgs g) {
     const float* Q1 = g.q_one_step + (long)(t - 1) * A * A;
     // true: softmax(log(onehot + eps)) @ Q2; pred: softmax(pred) @ Q2
     const float tmx = wave_max(fmaxf(tl0, tl1));
-    const float te0 = expf(tl0 - tmx), te1 = ok1 ? expf(tl1 - tmx) : 0.f;
+    const float te0 = ok0 ? expf(tl0 - tmx) : 0.f, te1 = ok1 ? expf(tl1 - tmx) : 0.f;
     const float tse = wave_sum(te0 + te1);
     float fp0 = 0.f, fp1 = 0.f, ft0 = 0.f, ft1 = 0.f;
     for (int cc = 0; cc < A; ++cc) {
       const float p = sm[cc];
       const float pt = __fdiv_rn(expf(logf(__fadd_rn(cc == x0 ? 1.0f : 0.0f, eps)) - tmx), tse);
-      fp0 = fmaf(p, Q2[cc * A + d0], fp0);
-      ft0 = fmaf(pt, Q2[cc * A + d0], ft0);
+      if (ok0) {
+        fp0 = fmaf(p, Q2[cc * A + d0], fp0);
+        ft0 = fmaf(pt, Q2[cc * A + d0], ft0);
+      }
       if (ok1) {
         fp1 = fmaf(p, Q2[cc * A + d1], fp1);
         ft1 = fmaf(pt, Q2[cc * A + d1], ft1);
       }
     }
-    const float f10 = logf(__fadd_rn(Q1[d0 * A + xt], eps));
-    q0 = __fadd_rn(f10, logf(__fadd_rn(fp0, eps)));
-    p0 = __fadd_rn(f10, logf(__fadd_rn(ft0, eps)));
+    if (ok0) {
+      const float f10 = logf(__fadd_rn(Q1[d0 * A + xt], eps));
+      q0 = __fadd_rn(f10, logf(__fadd_rn(fp0, eps)));
+      p0 = __fadd_rn(f10, logf(__fadd_rn(ft0, eps)));
+    }
     if (ok1) {
       const float f11 = logf(__fadd_rn(Q1[d1 * A + xt], eps));
       q1 = __fadd_rn(f11, logf(__fadd_rn(fp1, eps)));
@@ -942,19 +948,19 @@ __global__ __launch_bounds__(256) void k_train_node_loss(TrainArgs g) {
     }
   }
   // KL(C(p) || C(q)) with both logits shifted by eps (categorical_kl_logits)
-  const float a0 = p0 + eps, a1 = ok1 ? p1 + eps : -INFINITY;
-  const float b0 = q0 + eps, b1 = ok1 ? q1 + eps : -INFINITY;
+  const float a0 = ok0 ? p0 + eps : -INFINITY, a1 = ok1 ? p1 + eps : -INFINITY;
+  const float b0 = ok0 ? q0 + eps : -INFINITY, b1 = ok1 ? q1 + eps : -INFINITY;
   const float am = wave_max(fmaxf(a0, a1)), bm = wave_max(fmaxf(b0, b1));
-  const float ea0 = expf(a0 - am), ea1 = ok1 ? expf(a1 - am) : 0.f;
-  const float eb0 = expf(b0 - bm), eb1 = ok1 ? expf(b1 - bm) : 0.f;
+  const float ea0 = ok0 ? expf(a0 - am) : 0.f, ea1 = ok1 ? expf(a1 - am) : 0.f;
+  const float eb0 = ok0 ? expf(b0 - bm) : 0.f, eb1 = ok1 ? expf(b1 - bm) : 0.f;
   const float lsa = logf(wave_sum(ea0 + ea1)) + am, lsb = logf(wave_sum(eb0 + eb1)) + bm;
   const float sa = wave_sum(ea0 + ea1);
-  float kl = (ea0 / sa) * ((a0 - lsa) - (b0 - lsb));
+  float kl = ok0 ? (ea0 / sa) * ((a0 - lsa) - (b0 - lsb)) : 0.f;
   if (ok1) kl += (ea1 / sa) * ((a1 - lsa) - (b1 - lsb));
   kl = wave_sum(kl);
   // cross entropy of the predicted x_0 logits at a0
   const float lse = logf(se) + mx;
-  const float mine = (d0 == x0 ? lg0 : 0.f) + (ok1 && d1 == x0 ? lg1 : 0.f);
+  const float mine = (ok0 && d0 == x0 ? lg0 : 0.f) + (ok1 && d1 == x0 ? lg1 : 0.f);
   const float ce = lse - wave_sum(mine);
   if (lane == 0) {
     g.part[i * 2 + 0] = kl;

@@ -2229,6 +2229,23 @@ extern "C" int chm_edge_features(chm_batch* b, const float* x, float* feat, void
   return CHM_OK;
 }
 
+// The training kernels' arguments on the batch's decoder outputs (HO, LAT), for chm_training_loss and
+// chm_debug_train_update alike. The per-node partials go to Y (decoder scratch, free after the decoder call).
+static TrainArgs train_args(const chm_batch* b, const chm_train_tables* tt, const int64_t* d_t, const int64_t* a0,
+                            const float* x0, const float* l0, const float* rand_a, const float* noise_l,
+                            const float* noise_x, float* out, int64_t* a_t, float* x_t, float* l_t, float* target_x) {
+  TrainArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.N = b->N; g.B = b->B; g.A = b->m->d.max_atoms; g.T = tt->T; g.t = d_t; g.a0 = a0; g.x0 = x0; g.l0 = l0;
+  g.rand_a = rand_a; g.noise_l = noise_l; g.noise_x = noise_x; g.coef = tt->d_coef4;
+  g.q_one_step = tt->d_q_one_step; g.q_mats = tt->d_q_mats; g.n2g = b->n2g;
+  g.a_t = a_t; g.x_t = x_t; g.l_t = l_t; g.target_x = target_x;
+  g.hybrid = tt->hybrid_coeff; g.cost_a = tt->cost_atom_types; g.cost_l = tt->cost_lattice; g.cost_x = tt->cost_coords;
+  g.HO = b->HO; g.LAT = b->LAT; g.part = b->Y;
+  g.out = out;
+  return g;
+}
+
 extern "C" int chm_training_loss(chm_batch* b, const chm_train_tables* tt, const int64_t* d_t, const int64_t* a0,
                                  const float* x0, const float* l0, const float* temb, const float* text,
                                  const float* rand_a, const float* noise_l, const float* noise_x, float* out,
@@ -2244,15 +2261,7 @@ extern "C" int chm_training_loss(chm_batch* b, const chm_train_tables* tt, const
   hipStream_t s = (hipStream_t)stream;
   const long N = b->N;
   const int B = b->B;
-  TrainArgs g;
-  std::memset(&g, 0, sizeof(g));
-  g.N = N; g.B = B; g.A = m->d.max_atoms; g.T = tt->T; g.t = d_t; g.a0 = a0; g.x0 = x0; g.l0 = l0;
-  g.rand_a = rand_a; g.noise_l = noise_l; g.noise_x = noise_x; g.coef = tt->d_coef4;
-  g.q_one_step = tt->d_q_one_step; g.q_mats = tt->d_q_mats; g.n2g = b->n2g;
-  g.a_t = a_t; g.x_t = x_t; g.l_t = l_t; g.target_x = target_x;
-  g.hybrid = tt->hybrid_coeff; g.cost_a = tt->cost_atom_types; g.cost_l = tt->cost_lattice; g.cost_x = tt->cost_coords;
-  g.HO = b->HO; g.LAT = b->LAT; g.part = b->Y;  // (Y: decoder scratch, free after the call)
-  g.out = out;
+  const TrainArgs g = train_args(b, tt, d_t, a0, x0, l0, rand_a, noise_l, noise_x, out, a_t, x_t, l_t, target_x);
   HIPCHK(train_noise(g, s));
   int rc = run_decoder(b, 1, a_t, x_t, l_t, temb, m->d.time_dim, nullptr, text, nullptr, 3, s);
   if (rc) return rc;
@@ -2261,6 +2270,51 @@ extern "C" int chm_training_loss(chm_batch* b, const chm_train_tables* tt, const
   if (pred_coords)
     HIPCHK(hipMemcpy2DAsync(pred_coords, 3 * sizeof(float), b->HO + m->d.max_atoms, HEADS_N * sizeof(float),
                             3 * sizeof(float), N, hipMemcpyDeviceToDevice, s));
+  return CHM_OK;
+}
+
+// The training kernels on caller-supplied decoder outputs (tests/test_gpu_train_kernels.py): train_noise, then
+// train_loss, with chm_training_loss's TrainArgs and no decoder call between them. Every argument check runs before
+// the first HIP call, the batch-independent ones first, so a refused call needs no device.
+extern "C" int chm_debug_train_update(chm_batch* b, const chm_train_tables* tt, const int64_t* d_t, const int64_t* a0,
+                                      const float* x0, const float* l0, const float* rand_a, const float* noise_l,
+                                      const float* noise_x, const float* d_types, int64_t n_types,
+                                      const float* d_coords, int64_t n_coords, const float* d_lattice,
+                                      int64_t n_lattice, float* out, int64_t* a_t, float* x_t, float* l_t,
+                                      float* target_x, float* part, void* stream) {
+  auto bad = [&](const std::string& why) { return fail(CHM_E_ARG, "chm_debug_train_update: " + why); };
+  if (!tt) return bad("tables is NULL");
+  if (tt->T < 1) return bad("tables: T must be >= 1");
+  if (!tt->d_coef4 || !tt->d_q_one_step || !tt->d_q_mats) return bad("NULL table");
+  if (!d_t) return bad("d_t is NULL");
+  if (!a0 || !x0 || !l0) return bad(std::string(!a0 ? "d_a0" : !x0 ? "d_x0" : "d_l0") + " is NULL");
+  if (!rand_a || !noise_l || !noise_x) return bad("noise: all three buffers are required");
+  if (!d_types) return bad("d_types is NULL");
+  if (!d_coords) return bad("d_coords is NULL");
+  if (!d_lattice) return bad("d_lattice is NULL");
+  if (!out) return bad("d_out is NULL");
+  if (!a_t || !x_t || !l_t || !target_x) return bad("the noised-state outputs are required");
+  if (!part) return bad("d_part is NULL");
+  if (!b) return bad("batch is NULL");
+  const long N = b->N, B = b->B, A = b->m->d.max_atoms;
+  auto sized = [&](int64_t n, long expect, const char* name) -> int {
+    if (n != expect)
+      return bad(std::string(name) + ": " + std::to_string(n) + " elements, the batch needs " + std::to_string(expect));
+    return CHM_OK;
+  };
+  int rc;
+  if ((rc = sized(n_types, N * A, "n_types [N,A]"))) return rc;
+  if ((rc = sized(n_coords, N * 3, "n_coords [N,3]"))) return rc;
+  if ((rc = sized(n_lattice, B * 9, "n_lattice [B,3,3]"))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const TrainArgs g = train_args(b, tt, d_t, a0, x0, l0, rand_a, noise_l, noise_x, out, a_t, x_t, l_t, target_x);
+  HIPCHK(train_noise(g, s));
+  HIPCHK(copy_rows(d_types, A, b->HO, HEADS_N, N, (int)A, s));
+  HIPCHK(copy_rows(d_coords, 3, b->HO + A, HEADS_N, N, 3, s));
+  HIPCHK(hipMemcpyAsync(b->LAT, d_lattice, (size_t)B * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(train_loss(g, s));
+  HIPCHK(hipMemcpyAsync(part, g.part, (size_t)N * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
   return CHM_OK;
 }
 

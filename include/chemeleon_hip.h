@@ -423,6 +423,22 @@ int chm_debug_step_update(chm_batch* b, const chm_schedule* sched, int t, const 
                           const float* d_types, int64_t n_types, const float* d_coords, int64_t n_coords,
                           const float* d_lattice, int64_t n_lattice, int stage, void* stream);
 
+/* Test hook: the kernels of the training forward on caller-supplied decoder outputs, by the very code
+ * chm_training_loss runs around its decoder call (the same kernels, launched with arguments built by the same
+ * function) and with no decoder call: q_sample of (d_a0, d_x0, d_l0) at the per-graph d_t [B] (int64, 1..T; d_a0 in
+ * [0, A): neither is checked) with the caller's noise, as chm_training_loss takes it (d_noise_l already masked), then
+ * the D3PM hybrid loss and the two MSEs on d_types [N,A], d_coords [N,3], d_lattice [B,3,3], each with its ELEMENT
+ * count, as chm_decoder_forward with pairs = 1 returns them; they are packed into the batch's own head buffers (any
+ * max_pairs). Outputs, all required: d_out[6] as chm_training_loss, d_a_t [N] int64, d_x_t [N,3], d_l_t [B,3,3],
+ * d_target_x [N,3], and d_part [N,2] = each node's {KL, cross entropy}, whose means are d_out[1] and d_out[2].
+ * For tests only: it synchronises the stream. Every check (NULL pointers, T >= 1, element counts) returns CHM_E_ARG
+ * naming the field before the first HIP call, the ones that need no batch first, without a device. */
+int chm_debug_train_update(chm_batch* b, const chm_train_tables* tt, const int64_t* d_t, const int64_t* d_a0,
+                           const float* d_x0, const float* d_l0, const float* d_rand_a, const float* d_noise_l,
+                           const float* d_noise_x, const float* d_types, int64_t n_types, const float* d_coords,
+                           int64_t n_coords, const float* d_lattice, int64_t n_lattice, float* d_out, int64_t* d_a_t,
+                           float* d_x_t, float* d_l_t, float* d_target_x, float* d_part, void* stream);
+
 /* Test hook: one GEMM kernel of the decoder on caller-supplied fp32 device operands,
  * C[M,N] = epi(A[M,K] . W[N,K]^T), the weights packed exactly as chm_model_create packs them
  * (bf16 planes for kinds 1-3, row-scaled fp16 split rows in 16-column chunks for kind 4, in

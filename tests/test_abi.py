@@ -71,6 +71,9 @@ def test_null_handles_are_rejected():
     assert lib.chm_debug_step_update(None, ctypes.byref(sc), 1, None, 2.0, ctypes.byref(io), 0, 0, 0, x, 208, x, 6, x,
                                      18, 1, None) == -1
     assert b"batch" in lib.chm_last_error()
+    tt = _lib.chm_train_tables(100, x, x, x, 1.0, 1.0, 1.0, 1.0)
+    assert lib.chm_debug_train_update(None, ctypes.byref(tt), *([x] * 8), 208, x, 6, x, 18, *([x] * 6), None) == -1
+    assert b"chm_debug_train_update" in lib.chm_last_error() and b"batch" in lib.chm_last_error()
 
 
 def test_cpu_tensors_are_refused():
