@@ -464,6 +464,72 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> dedup(const at::Tensor& atom_type
   return {group, count, fp};
 }
 
+// Lattice system and reduced cell (chm_cell_run + chm_cell_apply): the state's cell records and the state in the
+// reduced cells -> (floats [B,8] = a, b, c, alpha, beta, gamma, volume, 0 of the reduced cell; ints [B,18] = T
+// (9, row-major), n_ops, n2, n3, n4, n6, system, halvings, flags, passes; frac [N,3] in the reduced basis;
+// lattices [B,3,3] reduced). require: the wanted system codes, int32 [1] or [B], or None. Plans are cached as
+// the screen's.
+struct CellPlans {
+  std::mutex mu;
+  std::vector<std::tuple<std::vector<int64_t>, int, chm_cell*>> plans;
+  chm_cell* get(const std::vector<int64_t>& natoms, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
+    std::vector<int32_t> nat;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "cell: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    chm_cell* p = nullptr;
+    check(chm_cell_create(nat.data(), (int)nat.size(), &p), "chm_cell_create");
+    if (plans.size() >= 8) {
+      chm_cell_destroy(std::get<2>(plans.front()));
+      plans.erase(plans.begin());
+    }
+    plans.emplace_back(natoms, device, p);
+    return p;
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> cell(const at::Tensor& frac, const at::Tensor& lattices,
+                                                                std::vector<int64_t> natoms,
+                                                                const c10::optional<at::Tensor>& require,
+                                                                double symprec, double angle_tolerance) {
+  static CellPlans* cache = new CellPlans;
+  TORCH_CHECK(!natoms.empty(), "cell: natoms is empty");
+  const c10::Device dev = frac.device();
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  const int32_t* rq = nullptr;
+  int64_t n_rq = 0;
+  if (require.has_value()) {
+    need_on(*require, dev, at::kInt, "require");
+    TORCH_CHECK(require->dim() == 1 && (require->size(0) == 1 || require->size(0) == B),
+                "require: expected shape [1] or [", B, "], got ", require->sizes());
+    rq = require->data_ptr<int32_t>();
+    n_rq = require->numel();
+  }
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  chm_cell* plan = cache->get(natoms, dev.index());
+  at::Tensor rec = at::empty({B, 128}, at::TensorOptions().dtype(at::kByte).device(dev));
+  at::Tensor x_out = at::empty_like(frac), lat_out = at::empty_like(lattices);
+  check(chm_cell_run(plan, lattices.data_ptr<float>(), lattices.numel(), rq, n_rq, (float)symprec,
+                     (float)angle_tolerance, rec.data_ptr(), (size_t)rec.numel(), stream()),
+        "chm_cell_run");
+  check(chm_cell_apply(plan, rec.data_ptr(), (size_t)rec.numel(), frac.data_ptr<float>(), frac.numel(),
+                       lattices.data_ptr<float>(), lattices.numel(), x_out.data_ptr<float>(), x_out.numel(),
+                       lat_out.data_ptr<float>(), lat_out.numel(), stream()),
+        "chm_cell_apply");
+  return {rec.view(at::kFloat).slice(1, 0, 8).contiguous(), rec.view(at::kInt).slice(1, 8, 26).contiguous(), x_out,
+          lat_out};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -492,6 +558,8 @@ TORCH_LIBRARY(chemeleon, m) {
         "float min_distance) -> (Tensor, Tensor)");
   m.def("dedup(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? exclude, float tol, "
         "float r_cut, float sigma, int bins) -> (Tensor, Tensor, Tensor)");
+  m.def("cell(Tensor frac, Tensor lattices, int[] natoms, Tensor? require, float symprec, float angle_tolerance) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -501,4 +569,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("d3pm_sample", d3pm_sample);
   m.impl("screen", screen);
   m.impl("dedup", dedup);
+  m.impl("cell", cell);
 }

@@ -247,27 +247,19 @@ def deduped_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, dedu
     """(representatives, DedupReport, ScreenReport or None): groups the state on the device (after the screen,
     whose failures are excluded) and copies and converts only the representatives, each with
     atoms.info["dedup"] (and info["screen"] with a screen)."""
-    from chemeleon_amd.modules.schema import step_to_atoms
+    from chemeleon_amd.screening import screen_states, selected_atoms
     nat = [int(n) for n in natoms]
     screened = None
     if screen is not None:
-        from chemeleon_amd.screening import screen_states
         screened = screen_states(nat, atom_types, frac_coords, lattices, screen)
     report = dedup_states(nat, atom_types, frac_coords, lattices, dedup,
                           None if screened is None else ~screened.valid)
     keep = np.flatnonzero(report.representative).tolist()
     if not keep:
         return [], report, screened
-    offs = np.concatenate([[0], np.cumsum(nat)])
-    rows = torch.cat([torch.arange(int(offs[g]), int(offs[g + 1])) for g in keep]).to(atom_types.device)
-    graphs = torch.tensor(keep, device=lattices.device)
-    atoms = step_to_atoms(atom_types.index_select(0, rows), frac_coords.index_select(0, rows),
-                          lattices.index_select(0, graphs), [nat[g] for g in keep])
+    atoms = selected_atoms(nat, atom_types, frac_coords, lattices, keep)
     for at, g in zip(atoms, keep):
-        info = getattr(at, "info", None)
-        if info is None:
-            info = at.info = {}
-        info["dedup"] = report.record(g)
+        at.info["dedup"] = report.record(g)
         if screened is not None:
-            info["screen"] = dict(screened.record(g), index=g)
+            at.info["screen"] = dict(screened.record(g), index=g)
     return atoms, report, screened

@@ -58,6 +58,7 @@ PATH_CHEMELEON_COMPOSITION = os.path.join(CHECKPOINT_DIR, "chemeleon-fksq6cgp.ck
 class Chemeleon(nn.Module):
     last_screen = None  # the ScreenReport of the last sample(..., screen=...) call
     last_dedup = None   # the DedupReport of the last sample(..., dedup=...) call
+    last_cell = None    # the CellReport of the last sample(..., cell=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
@@ -648,7 +649,7 @@ class Chemeleon(nn.Module):
 
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
-               group=None, overlap: bool = True, screen=None, dedup=None, **kw):
+               group=None, overlap: bool = True, screen=None, dedup=None, cell=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -682,8 +683,23 @@ class Chemeleon(nn.Module):
         the whole report is kept as self.last_dedup. With screen= as well the screen runs first and its failures
         take no part: they are neither returned nor representatives. Like the screen it is for finished
         structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
-        rank."""
+        rank.
+
+        cell=Cell(...) (chemeleon_amd.cell): the lattice of every finished structure is Niggli-reduced and its
+        lattice system found on the device, after the screen and before the grouping; each returned structure
+        gets atoms.info["cell"] and the whole report is kept as self.last_cell. With require= only the
+        structures of that lattice system are returned, and the others take no part in the grouping; with
+        reduce=True the returned structures are in their reduced cells. Like the screen it is for finished
+        structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
+        rank. Without the keyword nothing of it runs."""
         natoms = [n_atoms] * n_samples
+        if cell is not None:
+            from chemeleon_amd.cell import Cell, finished_atoms
+            if not isinstance(cell, Cell):
+                raise ValueError("cell must be a chemeleon_amd.Cell")
+            if stream or return_trajectory:
+                raise ValueError("cell= applies to finished structures: not with stream / return_trajectory")
+            cell.codes_for(n_samples)  # (a per-crystal list of the wrong length fails before sampling)
         if dedup is not None:
             from chemeleon_amd.dedup import Dedup, deduped_atoms
             if not isinstance(dedup, Dedup):
@@ -713,6 +729,13 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
+        if cell is not None:
+            atoms, self.last_cell, screened, grouped = finished_atoms(natoms, a, x, lat, cell, screen, dedup)
+            if screen is not None:
+                self.last_screen = screened
+            if dedup is not None:
+                self.last_dedup = grouped
+            return atoms
         if dedup is not None:
             atoms, self.last_dedup, screened = deduped_atoms(natoms, a, x, lat, dedup, screen)
             if screen is not None:

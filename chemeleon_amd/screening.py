@@ -192,23 +192,31 @@ def screen_states(natoms: Sequence[int], atom_types, frac_coords, lattices, scre
     return ScreenReport(host)
 
 
+def selected_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, keep: Sequence[int]):
+    """The crystals `keep` (indices into natoms, in order) of a device state as structures: only their rows are
+    copied and converted (schema.step_to_atoms); each gets an `info` dict if it has none."""
+    from chemeleon_amd.modules.schema import step_to_atoms
+    nat = [int(n) for n in natoms]
+    offs = np.concatenate([[0], np.cumsum(nat)])
+    rows = torch.cat([torch.arange(int(offs[g]), int(offs[g + 1])) for g in keep]).to(atom_types.device)
+    graphs = torch.tensor(list(keep), device=lattices.device)
+    atoms = step_to_atoms(atom_types.index_select(0, rows), frac_coords.index_select(0, rows),
+                          lattices.index_select(0, graphs), [nat[g] for g in keep])
+    for at in atoms:
+        if getattr(at, "info", None) is None:
+            at.info = {}
+    return atoms
+
+
 def screened_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen: Screen):
     """(passing structures, report): screens the state on the device, then copies and converts only the crystals
-    that pass (schema.step_to_atoms of those), each with atoms.info["screen"] = its record."""
-    from chemeleon_amd.modules.schema import step_to_atoms
+    that pass, each with atoms.info["screen"] = its record."""
     nat = [int(n) for n in natoms]
     report = screen_states(nat, atom_types, frac_coords, lattices, screen)
     keep = [g for g in range(len(nat)) if report.valid[g]]
     if not keep:
         return [], report
-    offs = np.concatenate([[0], np.cumsum(nat)])
-    rows = torch.cat([torch.arange(int(offs[g]), int(offs[g + 1])) for g in keep]).to(atom_types.device)
-    graphs = torch.tensor(keep, device=lattices.device)
-    atoms = step_to_atoms(atom_types.index_select(0, rows), frac_coords.index_select(0, rows),
-                          lattices.index_select(0, graphs), [nat[g] for g in keep])
+    atoms = selected_atoms(nat, atom_types, frac_coords, lattices, keep)
     for at, g in zip(atoms, keep):
-        info = getattr(at, "info", None)
-        if info is None:
-            info = at.info = {}
-        info["screen"] = dict(report.record(g), index=g)
+        at.info["screen"] = dict(report.record(g), index=g)
     return atoms, report

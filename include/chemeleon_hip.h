@@ -736,6 +736,95 @@ int chm_dedup_group(int64_t B, int K, const float* d_fp, int64_t n_fp, const int
                     int32_t* d_group, int64_t n_group, int32_t* d_count, int64_t n_count, void* d_workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Lattice system and reduced cell of finished structures on the device: what test_lattice_system_matching of the
+ * reference's scripts/evaluate.py asks of pymatgen / spglib on the host (the structure's atoms replaced by one
+ * H, SpacegroupAnalyzer(symprec=0.1, angle_tolerance=10).get_lattice_type()), so a question about the lattice
+ * alone. This is NOT a port of spglib: the definition below is this library's own, and how far the two agree
+ * on real samples has not been measured. The crystal system with the atoms (a space-group search) is not built.
+ * Lattices are row vectors (Cartesian = frac . L).
+ *
+ * Reduction. Niggli reduction (Krivy-Gruber, steps A1-A8 with the epsilon rules of Grosse-Kunstleve et al.) of
+ * each lattice: Lr = T L with T integer and det T = +1 (the handedness is kept). The comparisons are between
+ * squared lengths and use eps = 1e-5 V^(2/3). Where an off-diagonal term exceeds its diagonal one (|2 b.c| > b.b
+ * + eps in A5, likewise A6, A7) the step subtracts the whole multiple rint(b.c / b.b) at once, so that a cell
+ * sheared by k rows takes one pass and not k; on the boundary cases it takes the published unit step. It runs in
+ * fp64 on one lane; the rows are recomputed as T L from the input in every pass, each entry (t0 l0 + t1 l1) +
+ * t2 l2, so nothing drifts. At most 100 passes, and no entry of T beyond +-32 767 (a step that would exceed it is
+ * not taken): a cell that is not finished then keeps what it has and gets CHM_CELL_NOT_REDUCED. Lr is rounded to
+ * fp32 once; that fp32 cell is what the record describes, what the search runs on and what chm_cell_apply
+ * returns.
+ *
+ * Search. Every W with entries in {-1, 0, 1} and |det W| = 1 (6 960 of the 3^9 = 19 683 candidates; candidate
+ * index = sum_q (W[q] + 1) 3^q over the row-major entries q). With L' = W Lr, W is accepted when every row
+ * length of L' differs from Lr's by at most symprec (A) and every inter-row angle by at most angle_tolerance
+ * (degrees). fp32, every product and sum rounded on its own, L' entries (w0 l0 + w1 l1) + w2 l2, lengths and
+ * angles as in the screen (accurate sqrtf / acosf).
+ *
+ * Classification. n = the size of the accepted set; among its det = +1 members n2, n3, n4, n6 = the counts with
+ * trace -1, 0, 1, 2 (rotations of order 2, 3, 4, 6). (n, n2, n3, n4, n6) =
+ *   (2,0,0,0,0) triclinic   (4,1,0,0,0) monoclinic   (8,3,0,0,0) orthorhombic   (16,5,0,2,0) tetragonal
+ *   (12,3,2,0,0) rhombohedral   (24,7,2,0,2) hexagonal   (48,9,8,6,0) cubic
+ * Any other tuple means that the tolerant set is not a group: both tolerances are halved (exactly, in fp32) and
+ * the search runs again, at most 4 halvings; a cell that still matches nothing gets CHM_CELL_AMBIGUOUS and
+ * system -1, with the counts of the last level. The counts are integer sums: two runs, and a crystal alone or
+ * inside any batch, give the same bytes.
+ *
+ * Flags. CHM_CELL_NONFINITE: a non-finite lattice entry; CHM_CELL_DEGENERATE: |det L| (fp64) not > 0. Both skip
+ * the reduction and the search: system -1, T = identity, counts 0, and the lengths, angles and volume are the
+ * input cell's as in the screen (90 degrees where a row is zero). CHM_CELL_NOT_REDUCED skips the search too: the
+ * candidates W reach a lattice's symmetries only from a reduced basis, so an unreduced cell gets system -1 and
+ * counts 0 rather than a lower system than it has; its record describes T L for the T it reached. CHM_CELL_MISMATCH: a required system was
+ * given and the crystal's system (also -1) is another.
+ * d_require: the wanted system codes, int32: NULL with n_require = 0 (no requirement), [1] for every crystal,
+ * or [B] per crystal.
+ *
+ * chm_cell_apply writes, for the records of a run, the reduced lattices T L ([B,3,3], the bits the search saw)
+ * and per atom x' = frac(x adj(T)) in [0, 1) (adj(T) = T^-1 exactly since det T = 1, formed in 64-bit integers;
+ * fp64, rounded once) into
+ * caller buffers that must not be the inputs: the sampler's state is never changed in place.
+ * The plan holds the crystals' node offsets on the current device (create: as the screen's). run and apply take
+ * every buffer with its element count (the records with their byte count, 128 per crystal, 16-byte aligned);
+ * a NULL pointer, a mismatched count, symprec outside (0, 1] or angle_tolerance outside (0, 30] returns
+ * CHM_E_ARG naming the argument before the first HIP call and nothing is enqueued. They allocate nothing and do
+ * not synchronise: legal under stream capture. */
+#define CHM_CELL_TRICLINIC 0
+#define CHM_CELL_MONOCLINIC 1
+#define CHM_CELL_ORTHORHOMBIC 2
+#define CHM_CELL_TETRAGONAL 3
+#define CHM_CELL_RHOMBOHEDRAL 4
+#define CHM_CELL_HEXAGONAL 5
+#define CHM_CELL_CUBIC 6
+#define CHM_CELL_AMBIGUOUS 1     /* no holohedry matched after 4 halvings */
+#define CHM_CELL_MISMATCH 2      /* system != the required one (only with d_require) */
+#define CHM_CELL_NOT_REDUCED 4   /* the reduction hit its cap (100 passes, |T| entries 32 767): no system */
+#define CHM_CELL_DEGENERATE 8    /* volume not > 0 */
+#define CHM_CELL_NONFINITE 16    /* a non-finite lattice entry */
+#define CHM_CELL_MAX_SYMPREC 1.0f
+#define CHM_CELL_MAX_ANGLE_TOLERANCE 30.0f
+typedef struct {
+  float a, b, c;              /* lengths of the reduced rows, ascending (A) */
+  float alpha, beta, gamma;   /* angles in degrees between rows 1-2, 0-2, 0-1 */
+  float volume;               /* |det| of the reduced cell */
+  float reserved0;            /* written as 0 */
+  int32_t transform[9];       /* T, row-major: Lr = T L */
+  int32_t n_ops;              /* n */
+  int32_t n2, n3, n4, n6;
+  int32_t system;             /* CHM_CELL_TRICLINIC .. CHM_CELL_CUBIC, or -1 */
+  int32_t halvings;           /* halvings used, 0..4 */
+  int32_t flags;              /* CHM_CELL_* bits */
+  int32_t passes;             /* passes of the reduction */
+  int32_t reserved[6];        /* written as 0 */
+} chm_cell_record;            /* 128 bytes */
+typedef struct chm_cell chm_cell;
+int chm_cell_create(const int32_t* h_natoms, int num_graphs, chm_cell** out);
+void chm_cell_destroy(chm_cell* plan);
+int chm_cell_run(const chm_cell* plan, const float* d_lattices, int64_t n_lattices, const int32_t* d_require,
+                 int64_t n_require, float symprec, float angle_tolerance, void* d_out, size_t n_out_bytes,
+                 void* stream);
+int chm_cell_apply(const chm_cell* plan, const void* d_records, size_t n_record_bytes, const float* d_frac,
+                   int64_t n_frac, const float* d_lattices, int64_t n_lattices, float* d_frac_out,
+                   int64_t n_frac_out, float* d_lattices_out, int64_t n_lattices_out, void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
