@@ -16,7 +16,7 @@ Per crystal: Niggli reduction (Lr = T L, T integer with det +1), then the search
 entries in {-1, 0, 1} and |det W| = 1 that maps Lr onto itself within `symprec` (A, row lengths) and
 `angle_tolerance` (degrees, inter-row angles); the set's size and its rotation orders name the holohedry. A set
 that is no group halves both tolerances, at most four times. This is not a port of spglib: how far the two agree
-on real samples has not been measured, and the crystal system with the atoms (a space-group search) is not built
+on real samples has not been measured; the crystal system with the atoms is chemeleon_amd.symmetry
 ("Lattice system and reduced cell").
 """
 
@@ -244,29 +244,6 @@ def finished_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, cel
     screen runs first, then the cell, then the grouping, from which the failures of both (a screen flag; a
     required system not met) are excluded. Only the structures that pass are copied and converted (in their
     reduced cells with cell.reduce), each with atoms.info["cell"] (and info["screen"] / info["dedup"])."""
-    from chemeleon_amd.screening import screen_states, selected_atoms
-    nat = [int(n) for n in natoms]
-    screened = grouped = None
-    if screen is not None:
-        screened = screen_states(nat, atom_types, frac_coords, lattices, screen)
-    x_r, lat_r, report = _run(nat, atom_types, frac_coords, lattices, cell, cell.reduce)
-    failed = report.mismatch.copy()
-    if screened is not None:
-        failed |= ~screened.valid
-    if dedup is not None:
-        from chemeleon_amd.dedup import dedup_states
-        grouped = dedup_states(nat, atom_types, frac_coords, lattices, dedup, failed)
-        keep = np.flatnonzero(grouped.representative).tolist()
-    else:
-        keep = np.flatnonzero(~failed).tolist()
-    if not keep:
-        return [], report, screened, grouped
-    x, lat = (x_r, lat_r) if cell.reduce else (frac_coords, lattices)
-    atoms = selected_atoms(nat, atom_types, x, lat, keep)
-    for at, g in zip(atoms, keep):
-        at.info["cell"] = dict(report.record(g), index=g, reduced=cell.reduce)
-        if screened is not None:
-            at.info["screen"] = dict(screened.record(g), index=g)
-        if grouped is not None:
-            at.info["dedup"] = grouped.record(g)
-    return atoms, report, screened, grouped
+    from chemeleon_amd.finish import finish_atoms
+    atoms, reports = finish_atoms(natoms, atom_types, frac_coords, lattices, screen=screen, cell=_need_cell(cell), dedup=dedup)
+    return atoms, reports["cell"], reports.get("screen"), reports.get("dedup")

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/chemeleon_hip.h"
+#include "cell_shared.h"
 
 int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
 
@@ -29,11 +30,11 @@ int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_err
 
 namespace {
 
-constexpr int kBlock = 256;          // four waves per crystal
-constexpr int kCandidates = 19683;   // 3^9 = 76 * 256 + 227: the last pass has idle lanes
+using namespace chm_cellshared;  // dot3, angle_deg, the candidate test, the reduced cell: shared with symm.hip
+
+constexpr int kBlock = 256;          // four waves per crystal (kCandidates = 3^9 = 76 * 256 + 227: the last pass has idle lanes)
 constexpr int kMaxPasses = 100;      // cap of the reduction
 constexpr int kMaxEntry = 32767;     // cap of |T|'s entries: products of two stay inside 2^31 and far inside fp64
-constexpr int kMaxHalvings = 4;
 constexpr double kNiggliEps = 1.0e-5;  // times V^(2/3): the comparisons are between squared lengths
 
 int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
@@ -61,15 +62,7 @@ struct ApplyArgs {
   float* lat_out;
 };
 
-__device__ inline float dot3(const float* u, const float* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 __device__ inline double dot3d(const double* u, const double* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-// (as k_screen's: 90 where a row is zero)
-__device__ inline float angle_deg(const float* u, const float* v, float lu, float lv) {
-  const float d = lu * lv;
-  if (!(d > 0.f)) return 90.f;
-  const float cs = fminf(fmaxf(dot3(u, v) / d, -1.f), 1.f);
-  return acosf(cs) * 57.29577951308232f;
-}
 __device__ inline double det3d(const double* m) {
   return (m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6])) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
@@ -249,8 +242,9 @@ __global__ __launch_bounds__(kBlock) void k_cell(CellArgs p) {
   for (int q = 0; q < 9; ++q) L[q] = s_L[q];
   const bool skip = s_head[2] != 0;  // (uniform over the block: read behind the barrier)
   // the cell's own lengths and angles (every thread computes the same values)
-  const float l0 = sqrtf(dot3(L, L)), l1 = sqrtf(dot3(L + 3, L + 3)), l2 = sqrtf(dot3(L + 6, L + 6));
-  const float al = angle_deg(L + 3, L + 6, l1, l2), be = angle_deg(L, L + 6, l0, l2), ga = angle_deg(L, L + 3, l0, l1);
+  float len[3], ang[3];
+  cell_metric(L, len, ang);
+  const float l0 = len[0], l1 = len[1], l2 = len[2], al = ang[0], be = ang[1], ga = ang[2];
 
   int cnt[5] = {0, 0, 0, 0, 0};
   int code = -1, halvings = 0;
@@ -265,30 +259,8 @@ __global__ __launch_bounds__(kBlock) void k_cell(CellArgs p) {
         const int idx = base + tid;
         bool acc = false;
         int det = 0, tr = 0;
-        if (idx < kCandidates) {  // (tail lanes of the last pass take no part)
-          int W[9], r = idx;
-#pragma unroll
-          for (int q = 0; q < 9; ++q) {
-            W[q] = r % 3 - 1;
-            r /= 3;
-          }
-          det = (W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6])) +
-                W[2] * (W[3] * W[7] - W[4] * W[6]);
-          tr = W[0] + W[4] + W[8];
-          if (det == 1 || det == -1) {
-            float M[9];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int k = 0; k < 3; ++k)
-                M[3 * i + k] = ((float)W[3 * i] * L[k] + (float)W[3 * i + 1] * L[3 + k]) + (float)W[3 * i + 2] * L[6 + k];
-            const float m0 = sqrtf(dot3(M, M)), m1 = sqrtf(dot3(M + 3, M + 3)), m2 = sqrtf(dot3(M + 6, M + 6));
-            acc = fabsf(m0 - l0) <= tl && fabsf(m1 - l1) <= tl && fabsf(m2 - l2) <= tl;
-            if (acc)
-              acc = fabsf(angle_deg(M + 3, M + 6, m1, m2) - al) <= ta && fabsf(angle_deg(M, M + 6, m0, m2) - be) <= ta &&
-                    fabsf(angle_deg(M, M + 3, m0, m1) - ga) <= ta;
-          }
-        }
+        if (idx < kCandidates)  // (tail lanes of the last pass take no part)
+          acc = candidate_accepted(idx, L, len, ang, tl, ta, &det, &tr);
         const bool rot = acc && det == 1;
         w_n += __popcll(__ballot(acc));
         w_2 += __popcll(__ballot(rot && tr == -1));
@@ -338,38 +310,15 @@ __global__ __launch_bounds__(kBlock) void k_cell_apply(ApplyArgs p) {
   int T[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) T[q] = p.rec[g].transform[q];
-  if (tid < 9) {
-    const int i = tid / 3, k = tid - 3 * i;
-    const float* L = p.lat + (long)g * 9;
-    bool identity = true;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) identity &= T[q] == ((q % 4 == 0) ? 1 : 0);
-    // (T = identity copies the cell as it is: a flagged cell's NaN stays where it was, 0 * NaN would spread it)
-    p.lat_out[(long)g * 9 + tid] =
-        identity ? L[tid]
-                 : (float)(((double)T[3 * i] * (double)L[k] + (double)T[3 * i + 1] * (double)L[3 + k]) +
-                           (double)T[3 * i + 2] * (double)L[6 + k]);
-  }
-  // (64-bit: a product of two entries of a T that did not come from k_cell need not fit 32 bits)
-  long long t[9];
-#pragma unroll
-  for (int q = 0; q < 9; ++q) t[q] = T[q];
-  const double a00 = (double)(t[4] * t[8] - t[5] * t[7]), a01 = (double)(t[2] * t[7] - t[1] * t[8]),
-               a02 = (double)(t[1] * t[5] - t[2] * t[4]), a10 = (double)(t[5] * t[6] - t[3] * t[8]),
-               a11 = (double)(t[0] * t[8] - t[2] * t[6]), a12 = (double)(t[2] * t[3] - t[0] * t[5]),
-               a20 = (double)(t[3] * t[7] - t[4] * t[6]), a21 = (double)(t[1] * t[6] - t[0] * t[7]),
-               a22 = (double)(t[0] * t[4] - t[1] * t[3]);
+  if (tid < 9) p.lat_out[(long)g * 9 + tid] = reduced_entry(T, p.lat + (long)g * 9, tid);
+  double adj[9];
+  adjugate(T, adj);
   for (int i = tid; i < n; i += kBlock) {
     const long at = 3 * ((long)n0 + i);
-    const double x0 = (double)p.x[at], x1 = (double)p.x[at + 1], x2 = (double)p.x[at + 2];
-    const double y[3] = {(x0 * a00 + x1 * a10) + x2 * a20, (x0 * a01 + x1 * a11) + x2 * a21,
-                         (x0 * a02 + x1 * a12) + x2 * a22};
+    float f[3];
+    reduced_frac(adj, p.x + at, f);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float f = (float)(y[k] - floor(y[k]));
-      if (f >= 1.0f) f = 0.0f;  // (a value just below an integer rounds up to 1: the same point is 0)
-      p.x_out[at + k] = f;
-    }
+    for (int k = 0; k < 3; ++k) p.x_out[at + k] = f[k];
   }
 }
 

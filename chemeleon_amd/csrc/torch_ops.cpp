@@ -530,6 +530,81 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> cell(const at::Tensor
           lat_out};
 }
 
+// Crystal system with the atoms (chm_cell_run + chm_symm_run on one stream): (records uint8 [B,64] = the
+// chm_symm_record of every crystal; operations uint8 [B,48,16] = the slots of (int32 candidate index, float t[3]),
+// or [0,48,16] unless `operations`). require: the wanted crystal-system codes, int32 [1] or [B], or None. Plans
+// are cached as the screen's.
+struct SymmPlans {
+  std::mutex mu;
+  std::vector<std::tuple<std::vector<int64_t>, int, chm_cell*, chm_symm*>> plans;
+  std::pair<chm_cell*, chm_symm*> get(const std::vector<int64_t>& natoms, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return {std::get<2>(e), std::get<3>(e)};
+    std::vector<int32_t> nat;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "symmetry: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    chm_symm* s = nullptr;
+    check(chm_symm_create(nat.data(), (int)nat.size(), &s), "chm_symm_create");
+    chm_cell* c = nullptr;
+    const int rc = chm_cell_create(nat.data(), (int)nat.size(), &c);
+    if (rc != CHM_OK) {
+      chm_symm_destroy(s);
+      check(rc, "chm_cell_create");
+    }
+    if (plans.size() >= 8) {
+      chm_cell_destroy(std::get<2>(plans.front()));
+      chm_symm_destroy(std::get<3>(plans.front()));
+      plans.erase(plans.begin());
+    }
+    plans.emplace_back(natoms, device, c, s);
+    return {c, s};
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor> symmetry(const at::Tensor& atom_types, const at::Tensor& frac,
+                                            const at::Tensor& lattices, std::vector<int64_t> natoms,
+                                            const c10::optional<at::Tensor>& require, double symprec,
+                                            double angle_tolerance, bool operations) {
+  static SymmPlans* cache = new SymmPlans;
+  TORCH_CHECK(!natoms.empty(), "symmetry: natoms is empty");
+  const c10::Device dev = frac.device();
+  need_on(atom_types, dev, at::kLong, "atom_types");
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  need_shape(atom_types, {N}, "atom_types");
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  const int32_t* rq = nullptr;
+  int64_t n_rq = 0;
+  if (require.has_value()) {
+    need_on(*require, dev, at::kInt, "require");
+    TORCH_CHECK(require->dim() == 1 && (require->size(0) == 1 || require->size(0) == B),
+                "require: expected shape [1] or [", B, "], got ", require->sizes());
+    rq = require->data_ptr<int32_t>();
+    n_rq = require->numel();
+  }
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  auto plan = cache->get(natoms, dev.index());
+  const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+  at::Tensor cells = at::empty({B, 128}, bytes), rec = at::empty({B, 64}, bytes);
+  at::Tensor ops = at::empty({operations ? B : 0, 48, 16}, bytes);
+  check(chm_cell_run(plan.first, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, (float)symprec,
+                     (float)angle_tolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_symm_run(plan.second, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+                     atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
+                     lattices.numel(), rq, n_rq, (float)symprec, (float)angle_tolerance, rec.data_ptr(),
+                     (size_t)rec.numel(), operations ? ops.data_ptr() : nullptr, (size_t)ops.numel(), stream()),
+        "chm_symm_run");
+  return {rec, ops};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -560,6 +635,8 @@ TORCH_LIBRARY(chemeleon, m) {
         "float r_cut, float sigma, int bins) -> (Tensor, Tensor, Tensor)");
   m.def("cell(Tensor frac, Tensor lattices, int[] natoms, Tensor? require, float symprec, float angle_tolerance) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("symmetry(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? require, float symprec, "
+        "float angle_tolerance, bool operations) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -570,4 +647,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("screen", screen);
   m.impl("dedup", dedup);
   m.impl("cell", cell);
+  m.impl("symmetry", symmetry);
 }

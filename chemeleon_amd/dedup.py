@@ -247,19 +247,6 @@ def deduped_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, dedu
     """(representatives, DedupReport, ScreenReport or None): groups the state on the device (after the screen,
     whose failures are excluded) and copies and converts only the representatives, each with
     atoms.info["dedup"] (and info["screen"] with a screen)."""
-    from chemeleon_amd.screening import screen_states, selected_atoms
-    nat = [int(n) for n in natoms]
-    screened = None
-    if screen is not None:
-        screened = screen_states(nat, atom_types, frac_coords, lattices, screen)
-    report = dedup_states(nat, atom_types, frac_coords, lattices, dedup,
-                          None if screened is None else ~screened.valid)
-    keep = np.flatnonzero(report.representative).tolist()
-    if not keep:
-        return [], report, screened
-    atoms = selected_atoms(nat, atom_types, frac_coords, lattices, keep)
-    for at, g in zip(atoms, keep):
-        at.info["dedup"] = report.record(g)
-        if screened is not None:
-            at.info["screen"] = dict(screened.record(g), index=g)
-    return atoms, report, screened
+    from chemeleon_amd.finish import finish_atoms
+    atoms, reports = finish_atoms(natoms, atom_types, frac_coords, lattices, screen=screen, dedup=_need_dedup(dedup))
+    return atoms, reports["dedup"], reports.get("screen")

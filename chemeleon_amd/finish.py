@@ -1,0 +1,56 @@
+"""The tail of Chemeleon.sample(): the optional legs that run on the finished state on the device (the screen,
+chemeleon_amd.screening; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the grouping,
+chemeleon_amd.dedup), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
+
+from typing import Sequence
+
+import numpy as np
+
+
+def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen=None, cell=None, symmetry=None,
+                 dedup=None):
+    """(structures, reports): the tail of sample() with any of its four optional legs, in this order: the screen,
+    the cell, the symmetry, then the grouping, from which the failures of the first three (a screen flag; a
+    required lattice system or crystal system not met) are excluded. Only the structures that pass (with dedup:
+    one representative per group) are copied and converted (in their reduced cells with cell.reduce), each with
+    atoms.info["screen"] / ["cell"] / ["symmetry"] / ["dedup"] for the legs that ran. `reports` is a dict with the
+    report of each leg that ran under the same four names."""
+    from chemeleon_amd.screening import screen_states, selected_atoms
+    nat = [int(n) for n in natoms]
+    reports = {}
+    failed = None
+    x, lat = frac_coords, lattices
+    if screen is not None:
+        reports["screen"] = screen_states(nat, atom_types, frac_coords, lattices, screen)
+        failed = ~reports["screen"].valid
+    if cell is not None:
+        from chemeleon_amd.cell import _run
+        x_r, lat_r, reports["cell"] = _run(nat, atom_types, frac_coords, lattices, cell, cell.reduce)
+        failed = reports["cell"].mismatch.copy() if failed is None else failed | reports["cell"].mismatch
+        if cell.reduce:
+            x, lat = x_r, lat_r
+    if symmetry is not None:
+        from chemeleon_amd.symmetry import symmetry_states
+        reports["symmetry"] = symmetry_states(nat, atom_types, frac_coords, lattices, symmetry)
+        failed = reports["symmetry"].mismatch.copy() if failed is None else failed | reports["symmetry"].mismatch
+    if dedup is not None:
+        from chemeleon_amd.dedup import dedup_states
+        reports["dedup"] = dedup_states(nat, atom_types, frac_coords, lattices, dedup, failed)
+        keep = np.flatnonzero(reports["dedup"].representative).tolist()
+    elif failed is not None:
+        keep = np.flatnonzero(~failed).tolist()
+    else:
+        keep = list(range(len(nat)))
+    if not keep:
+        return [], reports
+    atoms = selected_atoms(nat, atom_types, x, lat, keep)
+    for at, g in zip(atoms, keep):
+        if "screen" in reports:
+            at.info["screen"] = dict(reports["screen"].record(g), index=g)
+        if "cell" in reports:
+            at.info["cell"] = dict(reports["cell"].record(g), index=g, reduced=cell.reduce)
+        if "symmetry" in reports:
+            at.info["symmetry"] = dict(reports["symmetry"].record(g), index=g)
+        if "dedup" in reports:
+            at.info["dedup"] = reports["dedup"].record(g)
+    return atoms, reports

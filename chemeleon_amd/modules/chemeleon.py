@@ -59,6 +59,7 @@ class Chemeleon(nn.Module):
     last_screen = None  # the ScreenReport of the last sample(..., screen=...) call
     last_dedup = None   # the DedupReport of the last sample(..., dedup=...) call
     last_cell = None    # the CellReport of the last sample(..., cell=...) call
+    last_symmetry = None  # the SymmetryReport of the last sample(..., symmetry=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
@@ -649,7 +650,8 @@ class Chemeleon(nn.Module):
 
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
-               group=None, overlap: bool = True, screen=None, dedup=None, cell=None, **kw):
+               group=None, overlap: bool = True, screen=None, dedup=None, cell=None, symmetry=None,
+               **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -691,23 +693,39 @@ class Chemeleon(nn.Module):
         structures of that lattice system are returned, and the others take no part in the grouping; with
         reduce=True the returned structures are in their reduced cells. Like the screen it is for finished
         structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
-        rank. Without the keyword nothing of it runs."""
+        rank. Without the keyword nothing of it runs.
+
+        symmetry=Symmetry(...) (chemeleon_amd.symmetry): the crystal system of every finished structure, with
+        its atoms, is found on the device, after the screen and the cell and before the grouping; each returned
+        structure gets atoms.info["symmetry"] and the whole report is kept as self.last_symmetry. With require=
+        only the structures of that crystal system are returned, and the others take no part in the grouping.
+        Like the screen it is for finished structures (ValueError with stream / return_trajectory) and runs on
+        the gathered final state on every rank. Without the keyword nothing of it runs."""
         natoms = [n_atoms] * n_samples
+        if symmetry is not None:
+            from chemeleon_amd.symmetry import MAX_ATOMS, Symmetry
+            if not isinstance(symmetry, Symmetry):
+                raise ValueError("symmetry must be a chemeleon_amd.Symmetry")
+            if stream or return_trajectory:
+                raise ValueError("symmetry= applies to finished structures: not with stream / return_trajectory")
+            symmetry.codes_for(n_samples)  # (a per-crystal list of the wrong length fails before sampling)
+            if n_atoms > MAX_ATOMS:  # (so does a crystal that the search cannot hold)
+                raise ValueError(f"symmetry= holds at most {MAX_ATOMS} atoms per crystal, got n_atoms={n_atoms}")
         if cell is not None:
-            from chemeleon_amd.cell import Cell, finished_atoms
+            from chemeleon_amd.cell import Cell
             if not isinstance(cell, Cell):
                 raise ValueError("cell must be a chemeleon_amd.Cell")
             if stream or return_trajectory:
                 raise ValueError("cell= applies to finished structures: not with stream / return_trajectory")
             cell.codes_for(n_samples)  # (a per-crystal list of the wrong length fails before sampling)
         if dedup is not None:
-            from chemeleon_amd.dedup import Dedup, deduped_atoms
+            from chemeleon_amd.dedup import Dedup
             if not isinstance(dedup, Dedup):
                 raise ValueError("dedup must be a chemeleon_amd.Dedup")
             if stream or return_trajectory:
                 raise ValueError("dedup= applies to finished structures: not with stream / return_trajectory")
         if screen is not None:
-            from chemeleon_amd.screening import Screen, screened_atoms
+            from chemeleon_amd.screening import Screen
             if not isinstance(screen, Screen):
                 raise ValueError("screen must be a chemeleon_amd.Screen")
             if stream or return_trajectory:
@@ -729,20 +747,11 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
-        if cell is not None:
-            atoms, self.last_cell, screened, grouped = finished_atoms(natoms, a, x, lat, cell, screen, dedup)
-            if screen is not None:
-                self.last_screen = screened
-            if dedup is not None:
-                self.last_dedup = grouped
-            return atoms
-        if dedup is not None:
-            atoms, self.last_dedup, screened = deduped_atoms(natoms, a, x, lat, dedup, screen)
-            if screen is not None:
-                self.last_screen = screened
-            return atoms
-        if screen is not None:
-            atoms, self.last_screen = screened_atoms(natoms, a, x, lat, screen)
+        if screen is not None or cell is not None or symmetry is not None or dedup is not None:
+            from chemeleon_amd.finish import finish_atoms
+            atoms, reports = finish_atoms(natoms, a, x, lat, screen=screen, cell=cell, symmetry=symmetry, dedup=dedup)
+            for leg, report in reports.items():  # (only the legs that were asked for: the others keep their last)
+                setattr(self, "last_" + leg, report)
             return atoms
         return step_to_atoms(a, x, lat, natoms)
 

@@ -211,12 +211,6 @@ def selected_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, kee
 def screened_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen: Screen):
     """(passing structures, report): screens the state on the device, then copies and converts only the crystals
     that pass, each with atoms.info["screen"] = its record."""
-    nat = [int(n) for n in natoms]
-    report = screen_states(nat, atom_types, frac_coords, lattices, screen)
-    keep = [g for g in range(len(nat)) if report.valid[g]]
-    if not keep:
-        return [], report
-    atoms = selected_atoms(nat, atom_types, frac_coords, lattices, keep)
-    for at, g in zip(atoms, keep):
-        at.info["screen"] = dict(report.record(g), index=g)
-    return atoms, report
+    from chemeleon_amd.finish import finish_atoms
+    atoms, reports = finish_atoms(natoms, atom_types, frac_coords, lattices, screen=Screen() if screen is None else screen)
+    return atoms, reports["screen"]

@@ -740,7 +740,7 @@ int chm_dedup_group(int64_t B, int K, const float* d_fp, int64_t n_fp, const int
  * reference's scripts/evaluate.py asks of pymatgen / spglib on the host (the structure's atoms replaced by one
  * H, SpacegroupAnalyzer(symprec=0.1, angle_tolerance=10).get_lattice_type()), so a question about the lattice
  * alone. This is NOT a port of spglib: the definition below is this library's own, and how far the two agree
- * on real samples has not been measured. The crystal system with the atoms (a space-group search) is not built.
+ * on real samples has not been measured. The crystal system with the atoms is chm_symm_*, below.
  * Lattices are row vectors (Cartesian = frac . L).
  *
  * Reduction. Niggli reduction (Krivy-Gruber, steps A1-A8 with the epsilon rules of Grosse-Kunstleve et al.) of
@@ -824,6 +824,106 @@ int chm_cell_run(const chm_cell* plan, const float* d_lattices, int64_t n_lattic
 int chm_cell_apply(const chm_cell* plan, const void* d_records, size_t n_record_bytes, const float* d_frac,
                    int64_t n_frac, const float* d_lattices, int64_t n_lattices, float* d_frac_out,
                    int64_t n_frac_out, float* d_lattices_out, int64_t n_lattices_out, void* stream);
+
+/* Crystal system with the atoms of finished structures on the device: what test_crystal_system_matching of the
+ * reference's scripts/evaluate.py asks of pymatgen / spglib on the host
+ * (SpacegroupAnalyzer(st, symprec=0.1, angle_tolerance=10).get_crystal_system()). This is NOT a port of spglib:
+ * the definition below is this library's own, and how far the two agree on real samples has not been measured.
+ *
+ * Input per crystal. The state (atom_types int64 [N], compared as their low 32 bits; frac fp32 [N,3]; lattices
+ * fp32 [B,3,3]) and the crystal's chm_cell_record from a run of chm_cell_run on the same lattices with the same
+ * symprec and angle_tolerance. The record supplies T, system, halvings, n_ops and flags.
+ *
+ * Basis. Lr = T L and x' = frac(x adj(T)) are exactly what chm_cell_apply produces, with the same bits (the same
+ * device code).
+ *
+ * Lattice operations. The set {W} is what the cell search accepted at the record's final level: tolerances
+ * symprec 2^-halvings and angle_tolerance 2^-halvings of the cell record, the same candidates in the same order,
+ * the same fp32 arithmetic (the same device function). A record with system < 0 (flagged or ambiguous), or whose
+ * n_ops is not the size of the set found again (a record of other lattices or tolerances), gets
+ * CHM_SYMM_NO_LATTICE, system -1, lattice_system -1, counts 0, tol 0.
+ *
+ * Action. W with L' = W Lr acts on fractional row vectors as x -> x W + t, component k being
+ * (x0 W[0][k] + x1 W[1][k]) + x2 W[2][k].
+ *
+ * Pivot. The pivot species is the atom type with the fewest atoms in the crystal, ties to the smallest type
+ * value; the pivot atom p is its first atom in node order. For each W the candidate translations are
+ * t_j = x'_j - x'_p W, one for every atom j of the pivot species in node order (n_pivot of them), not wrapped.
+ *
+ * Acceptance. (W, t_j) is accepted at tolerance tol when every atom i has an atom k of the same type with
+ * d = (x'_i W + t_j) - x'_k, d -= rintf(d) per component, c = d Lr with entries (d0 l0 + d1 l1) + d2 l2, and
+ * (c0 c0 + c1 c1) + c2 c2 <= tol tol. All fp32, every product and sum rounded on its own, no contraction.
+ *
+ * Thin cells. One image per component is exact only while 2 tol is below the smallest plane spacing of Lr. With
+ * rows a0, a1, a2: c0 = a1 x a2, c1 = a2 x a0, c2 = a0 x a1 (each component u v - w z of two rounded products),
+ * V = |(a0[0] c0[0] + a0[1] c0[1]) + a0[2] c0[2]|, spacing_i = V / sqrtf((ci[0] ci[0] + ci[1] ci[1]) + ci[2] ci[2]),
+ * all fp32. A crystal where not 2 symprec < fminf(fminf(spacing_0, spacing_1), spacing_2) gets CHM_SYMM_THIN, system -1,
+ * counts 0 and tol = symprec: wrong answers on needle cells are worse than none.
+ *
+ * Counts, from the accepted set: n_sym accepted pairs; n_trans pairs with W = I (>= 1 for finite coordinates);
+ * n_pg distinct W with at least one accepted translation; inversion, whether -I is among them; n_proper = m, the
+ * number of distinct proper parts det(W) W of those W, and n2, n3, n4, n6 = how many of the proper parts have
+ * trace -1, 0, 1, 2. The tuple (m, n2, n3, n4, n6) names the rotation group of the Laue class, hence the system:
+ *   (1,0,0,0,0) 1 triclinic      (2,1,0,0,0) 2 monoclinic      (4,3,0,0,0) 222 orthorhombic
+ *   (4,1,0,2,0) 4 tetragonal     (8,5,0,2,0) 422 tetragonal    (3,0,2,0,0) 3 trigonal     (6,3,2,0,0) 32 trigonal
+ *   (6,1,2,0,2) 6 hexagonal      (12,7,2,0,2) 622 hexagonal    (12,3,8,0,0) 23 cubic      (24,9,8,6,0) 432 cubic
+ * The set counts as a group only if the tuple is in the table, n_sym == n_pg n_trans and
+ * n_pg == m (1 + inversion). Otherwise tol is halved (exactly, in fp32; it starts at symprec) and the atom search
+ * runs again on the same {W}, at most 4 halvings; after the last the crystal gets CHM_SYMM_AMBIGUOUS and system
+ * -1, with the last level's counts. The names are pymatgen's: code 4 is "trigonal" here, while the same code of
+ * the lattice (CHM_CELL_RHOMBOHEDRAL) is "rhombohedral": a trigonal crystal may sit on a hexagonal lattice.
+ * All counts are integer sums: two runs, and a crystal alone or inside any batch, give the same bytes.
+ *
+ * Deliberately not built: the reduction to a primitive cell. When n_trans > 1 the answer describes the cell as
+ * given, so a supercell whose lattice has lower symmetry than the primitive lattice (a 2x1x1 cell of CsCl)
+ * reports the lower system (tetragonal); n_trans is in the record so that a caller can tell. The space-group
+ * number and the point group's name are not built either.
+ *
+ * CHM_SYMM_MISMATCH and d_require work as in the cell run, with crystal-system codes. The optional second output
+ * d_ops (may be NULL with n_ops_bytes = 0) holds CHM_SYMM_MAX_OPS slots of 16 bytes per crystal: int32 candidate
+ * index (as in the cell search) and float t[3]; one slot per distinct accepted W of the deciding level, in
+ * ascending candidate index, with that W's first accepted translation in pivot order; unused slots hold index -1
+ * and zeros. The plan holds the node offsets on the current device (create: as the cell's; a crystal of more than
+ * 256 atoms does not fit the staging and is refused with CHM_E_UNSUPPORTED). The run takes every buffer with its
+ * count (cell records 128 bytes, out 64 bytes per crystal, both and d_ops 16-byte aligned); a NULL pointer, a
+ * mismatched count or tolerances outside the cell run's limits return CHM_E_ARG naming the argument before the
+ * first HIP call and nothing is enqueued. It allocates nothing and does not synchronise: legal under stream
+ * capture. */
+#define CHM_SYMM_TRICLINIC 0
+#define CHM_SYMM_MONOCLINIC 1
+#define CHM_SYMM_ORTHORHOMBIC 2
+#define CHM_SYMM_TETRAGONAL 3
+#define CHM_SYMM_TRIGONAL 4
+#define CHM_SYMM_HEXAGONAL 5
+#define CHM_SYMM_CUBIC 6
+#define CHM_SYMM_AMBIGUOUS 1     /* no group matched after 4 halvings */
+#define CHM_SYMM_MISMATCH 2      /* system != the required one (only with d_require) */
+#define CHM_SYMM_NO_LATTICE 4    /* the cell record has no lattice system (or is not this lattice's) */
+#define CHM_SYMM_THIN 8          /* 2 symprec is not below the smallest plane spacing of the reduced cell */
+#define CHM_SYMM_MAX_OPS 48
+typedef struct {
+  int32_t system;             /* CHM_SYMM_TRICLINIC .. CHM_SYMM_CUBIC, or -1 */
+  int32_t n_sym;              /* accepted (W, t) pairs */
+  int32_t n_trans;            /* pure translations among them */
+  int32_t n_pg;               /* distinct W with a translation */
+  int32_t n_proper;           /* m */
+  int32_t n2, n3, n4, n6;
+  int32_t inversion;          /* 1 if -I is in the point group */
+  int32_t halvings;           /* halvings of tol used, 0..4 */
+  int32_t flags;              /* CHM_SYMM_* bits */
+  int32_t n_pivot;            /* atoms of the pivot species */
+  int32_t lattice_system;     /* copied from the cell record (-1 with CHM_SYMM_NO_LATTICE) */
+  float tol;                  /* the tolerance of the level that decided */
+  int32_t reserved;           /* written as 0 */
+} chm_symm_record;            /* 64 bytes */
+typedef struct chm_symm chm_symm;
+int chm_symm_create(const int32_t* h_natoms, int num_graphs, chm_symm** out);
+void chm_symm_destroy(chm_symm* plan);
+int chm_symm_run(const chm_symm* plan, const void* d_cell_records, size_t n_record_bytes, const int64_t* d_atom_types,
+                 int64_t n_atom_types, const float* d_frac, int64_t n_frac, const float* d_lattices,
+                 int64_t n_lattices, const int32_t* d_require, int64_t n_require, float symprec,
+                 float angle_tolerance, void* d_out, size_t n_out_bytes, void* d_ops, size_t n_ops_bytes,
+                 void* stream);
 
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
