@@ -78,6 +78,15 @@ class chm_debug_gemm_args(ctypes.Structure):
                 ("d_cmax", c_void_p)]
 
 
+class chm_debug_node_io(ctypes.Structure):
+    """The operands of one node-side stage with their element counts (test hook chm_debug_node_stage)."""
+    _fields_ = [("d_temb", c_void_p), ("n_temb", c_i64), ("d_t", c_void_p), ("n_t", c_i64),
+                ("tstride", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [f for name in ("text0", "text1", "cin", "a", "lat", "Y", "cemb", "HO", "Hres", "gbias", "Hl", "rmax",
+                               "split", "exp", "flags", "Hf", "LAT", "types", "coords")
+                for f in (("d_" + name, c_void_p), ("n_" + name, c_i64))]
+
+
 def step_io(a, x, lat, cond=None, null=None, noise=None, node0: int = 0, graph0: int = 0, nodes: int = None,
             graphs: int = None):
     """chm_step_io over tensors: the state (a [N] int64, x [N,3], lat [B,3,3]), conditioning rows
@@ -143,6 +152,8 @@ SIGNATURES = {
     "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
     "chm_debug_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                      c_void_p, c_void_p, c_void_p]),
+    "chm_debug_node_stage": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(chm_debug_node_io), c_void_p]),
+    "chm_debug_node_flag_words": (c_i64, [c_void_p, c_int, ctypes.POINTER(c_i64)]),
     "chm_debug_layer_jobs": (c_i64, [c_i64, c_int, c_int, ctypes.POINTER(c_i64), c_i64]),
     "chm_debug_layer_seq": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
     "chm_debug_pair_plan": (c_i64, [ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32),

@@ -1567,6 +1567,75 @@ static int edge_block(chm_batch* b, int P, int l, const EdgePlan& ep, bool ps, h
   return CHM_OK;
 }
 
+// The decoder's node-side glue launches (everything of a decoder call that is neither a GEMM nor the message path),
+// each with its arguments built from the batch, the call's EdgePlan and P: run_decoder and chm_debug_node_stage
+// call these same functions.
+// row k (RMX_*) of the split16 node GEMMs' row-max arrays, null where the plan keeps none
+static float* rmx_row(const chm_batch* b, const EdgePlan& ep, int k) {
+  return ep.n16 && !ep.ps ? b->rmx + k * ((long)b->P * b->N) : nullptr;
+}
+// cin [P,B,TD+X] = [time embedding | text rows]
+static int node_cond_in(chm_batch* b, int P, const float* temb, int tstride, const int* d_t, const float* text0,
+                        const float* text1, hipStream_t s) {
+  HIPCHK(build_cond_in(temb, tstride, d_t, text0, text1, b->m->d.text_dim, b->cin, b->B, P, s));
+  return CHM_OK;
+}
+// the embedding rows and the first kGBLayers layers' per-graph terms of edge layer 1 in one launch
+// (the pair grid's repair requests and per-layer flags start clear in every call: zeroed by this launch, two
+// memset nodes less per call)
+static int node_embed(chm_batch* b, const EdgePlan& ep, int P, const int64_t* a, const float* lat, hipStream_t s) {
+  const chm_model* m = b->m;
+  const int L = m->d.num_layers;
+  const bool ps = ep.ps, zero_grid = ep.zero_grid;
+  GraphBiasArgs ga0;
+  const int nl0 = L < kGBLayers ? L : kGBLayers;
+  for (int l = 0; l < nl0; ++l) {
+    ga0.Wc[l] = m->layers[l].Wcl;
+    ga0.b1[l] = m->layers[l].b1;
+  }
+  HIPCHK(embed(a, m->emb, b->Hres, b->N, P, s, rmx_row(b, ep, RMX_H), ps ? b->Hs : nullptr, ps ? b->He : nullptr, lat,
+               nl0 > 0 ? &ga0 : nullptr, nl0, 9, b->gbias, b->B, zero_grid ? b->xbad : nullptr,
+               zero_grid ? 2L * kMaxLayers : 0L, zero_grid ? b->psched : nullptr,
+               zero_grid ? (long)L * 8 * b->pplan.npx : 0L));
+  return CHM_OK;
+}
+// the per-graph terms of layers past the first kGBLayers
+static int node_graph_bias_rest(chm_batch* b, const float* lat, hipStream_t s) {
+  const chm_model* m = b->m;
+  const int L = m->d.num_layers, B = b->B;
+  for (int l0 = kGBLayers; l0 < L; l0 += kGBLayers) {
+    GraphBiasArgs ga;
+    const int nl = L - l0 < kGBLayers ? L - l0 : kGBLayers;
+    for (int l = 0; l < nl; ++l) {
+      ga.Wc[l] = m->layers[l0 + l].Wcl;
+      ga.b1[l] = m->layers[l0 + l].b1;
+    }
+    HIPCHK(graph_bias(lat, ga, nl, 9, b->gbias + (size_t)l0 * B * H, B, s));
+  }
+  return CHM_OK;
+}
+// FiLM + residual + layer l's LayerNorm (film-less: the LayerNorm only)
+static int node_film_ln(chm_batch* b, const EdgePlan& ep, int P, int l, hipStream_t s) {
+  const chm_model* m = b->m;
+  const LayerW& w = m->layers[l];
+  const bool ps = ep.ps;
+  HIPCHK(film_ln(m->film ? b->Y : nullptr, b->Hres, b->Hl, b->cemb, b->n2g, b->N, b->B, P, m->fw, m->fb, w.lw, w.lb, s,
+                 rmx_row(b, ep, 0), (long)b->P * b->N, ps ? b->Hls : nullptr, ps ? b->Hle : nullptr));
+  return CHM_OK;
+}
+static int node_final_ln(chm_batch* b, int P, hipStream_t s) {
+  HIPCHK(layer_norm(b->Hres, b->Hf, (long)P * b->N, b->m->flw, b->m->flb, s));
+  return CHM_OK;
+}
+static int node_graph_heads(chm_batch* b, int P, const float* lat, hipStream_t s) {
+  HIPCHK(graph_heads(b->Hf, b->m->Wlat, lat, b->node_off, b->natoms, b->N, b->B, P, b->LAT, s));
+  return CHM_OK;
+}
+static int node_split_heads(chm_batch* b, int P, float* types, float* coords, hipStream_t s) {
+  HIPCHK(split_heads(b->HO, (long)P * b->N, b->m->d.max_atoms, types, coords, s));
+  return CHM_OK;
+}
+
 // reuse_cond: the FiLM conditioning (cond_in + the conditioning MLP) of the previous call on this batch
 // is still valid (same t and text: the corrector call of a reverse step, chemeleon.py:438-448)
 static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, const float* lat, const float* temb,
@@ -1578,42 +1647,21 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
     if (rc) return rc;
   }
   const int L = m->d.num_layers, X = m->d.text_dim, B = b->B;
-  const long N = b->N, E = b->E, R = (long)P * N;
+  const long N = b->N, R = (long)P * N;
   const int CIN = TD + X;
   ProfScope whole(CHM_K_DECODER, s);
   const EdgePlan ep = edge_plan(b, P);
-  const bool n16 = ep.n16, ps = ep.ps, pairs = ep.pairs, zero_grid = ep.zero_grid;
-  const long RS = (long)b->P * N;
-  auto rmx = [&](int k) { return n16 && !ps ? b->rmx + k * RS : nullptr; };
+  const bool ps = ep.ps;
+  auto rmx = [&](int k) { return rmx_row(b, ep, k); };
   if (m->film && !reuse_cond) {
-    HIPCHK(build_cond_in(temb, tstride, d_t, text0, text1, X, b->cin, B, P, s));
+    if (const int rc = node_cond_in(b, P, temb, tstride, d_t, text0, text1, s)) return rc;
     GemmArgs g = gargs((long)P * B, 2 * H, CIN, b->cin, CIN, m->Wc, b->cemb, 2 * H);
     g.bias = m->bc; g.act = 1;
     HIPCHK(run_gemm(b, g, EPI_STD, m->Wc3, s));
   }
-  // (the pair grid's repair requests and per-layer flags start clear in every call: zeroed by the embedding launch
-  // below, two memset nodes less per call)
-  // the embedding rows and the first kGBLayers layers' per-graph terms of edge layer 1 in one launch
-  GraphBiasArgs ga0;
-  const int nl0 = L < kGBLayers ? L : kGBLayers;
-  for (int l = 0; l < nl0; ++l) {
-    ga0.Wc[l] = m->layers[l].Wcl;
-    ga0.b1[l] = m->layers[l].b1;
-  }
-  HIPCHK(embed(a, m->emb, b->Hres, N, P, s, rmx(RMX_H), ps ? b->Hs : nullptr, ps ? b->He : nullptr, lat,
-               nl0 > 0 ? &ga0 : nullptr, nl0, 9, b->gbias, B, zero_grid ? b->xbad : nullptr,
-               zero_grid ? 2L * kMaxLayers : 0L, zero_grid ? b->psched : nullptr,
-               zero_grid ? (long)L * 8 * b->pplan.npx : 0L));
+  if (const int rc = node_embed(b, ep, P, a, lat, s)) return rc;
   if (const int rc = edge_features(b, ep, x, s)) return rc;
-  for (int l0 = kGBLayers; l0 < L; l0 += kGBLayers) {  // the per-graph terms of layers past the first 16
-    GraphBiasArgs ga;
-    const int nl = L - l0 < kGBLayers ? L - l0 : kGBLayers;
-    for (int l = 0; l < nl; ++l) {
-      ga.Wc[l] = m->layers[l0 + l].Wcl;
-      ga.b1[l] = m->layers[l0 + l].b1;
-    }
-    HIPCHK(graph_bias(lat, ga, nl, 9, b->gbias + (size_t)l0 * B * H, B, s));
-  }
+  if (const int rc = node_graph_bias_rest(b, lat, s)) return rc;
   if (const int rc = clear_edge_flags(b, ep, s, false)) return rc;
   for (int l = 0; l < L; ++l) {
     const LayerW& w = m->layers[l];
@@ -1623,9 +1671,7 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
       if (ps) g.aex = b->He;
       HIPCHK(run_gemm(b, g, EPI_STD, m->Wp3, s, m->Wp16, m->Wpsc));
     }
-    // FiLM + residual + the layer's LayerNorm (film-less: the LayerNorm only)
-    HIPCHK(film_ln(m->film ? b->Y : nullptr, b->Hres, b->Hl, b->cemb, b->n2g, N, B, P, m->fw, m->fb, w.lw, w.lb, s,
-                   rmx(0), RS, ps ? b->Hls : nullptr, ps ? b->Hle : nullptr));
+    if (const int rc = node_film_ln(b, ep, P, l, s)) return rc;
     {  // per-node halves of the first edge layer: [P | Q] = Hl [A ; Bm]^T, P += b1 + C vec(LL^T)
       GemmArgs g = gargs(R, 2 * H, H, ps ? (const float*)b->Hls : b->Hl, H, w.WAB, b->PQ, 2 * H);
       g.gb = b->gbias + (size_t)l * B * H; g.ldgb = H; g.gb_cols = H; g.row2g = b->n2g; g.gb_rowmod = N;
@@ -1655,13 +1701,14 @@ static int run_decoder(chm_batch* b, int P, const int64_t* a, const float* x, co
       HIPCHK(run_gemm(b, g, EPI_STD, w.W43, s, w.W416, w.W4sc));
     }
   }
-  HIPCHK(layer_norm(b->Hres, b->Hf, R, m->flw, m->flb, s));
+  if (const int rc = node_final_ln(b, P, s)) return rc;
   if (heads & 1) {
     GemmArgs g = gargs(R, HEADS_N, H, b->Hf, H, m->Whead, b->HO, HEADS_N);
     g.bias = m->bhead;
     HIPCHK(run_gemm(b, g, EPI_STD, m->Whead3, s));  // (bf16x3: A is LayerNorm output, M small)
   }
-  if (heads & 2) HIPCHK(graph_heads(b->Hf, m->Wlat, lat, b->node_off, b->natoms, N, B, P, b->LAT, s));
+  if (heads & 2)
+    if (const int rc = node_graph_heads(b, P, lat, s)) return rc;
   return CHM_OK;
 }
 
@@ -1680,7 +1727,8 @@ extern "C" int chm_decoder_forward(chm_batch* b, int pairs, const int64_t* a, co
   int rc = run_decoder(b, pairs, a, x, lat, temb, time_stride, nullptr, t0, t1, heads, s);
   if (rc) return rc;
   const long R = (long)pairs * b->N;
-  if (heads & 1) HIPCHK(split_heads(b->HO, R, b->m->d.max_atoms, types_out, coords_out, s));
+  if (heads & 1)
+    if (const int rc = node_split_heads(b, pairs, types_out, coords_out, s)) return rc;
   if (lattice_out)
     HIPCHK(hipMemcpyAsync(lattice_out, b->LAT, (size_t)pairs * b->B * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (node_out) HIPCHK(hipMemcpyAsync(node_out, b->Hf, (size_t)R * H * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -2218,6 +2266,194 @@ extern "C" int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const fl
     if (const int rc = run(true)) return rc;
     HIPCHK(hipMemcpyAsync(d_agg_split, b->aggs, (size_t)pairs * N * H * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(d_agg_exp, b->agge, (size_t)pairs * N * sizeof(int), hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return CHM_OK;
+}
+
+// The words the embedding launch clears on a pair-grid plan, as chm_debug_node_stage's d_flags holds them: xbad
+// [2 kMaxLayers], then the pair grid's per-layer flags [L 8 npx], then the unused words up to the end of that
+// buffer's 256-byte-rounded allocation (the guard: no launch may write them). 0: the plan clears nothing.
+static long node_flag_words(const chm_batch* b, const EdgePlan& ep, long* n_psched) {
+  if (!ep.zero_grid) return 0;
+  const long np = (long)b->m->d.num_layers * 8 * b->pplan.npx;
+  if (n_psched) *n_psched = np;
+  return 2L * kMaxLayers + (np + 63) / 64 * 64;
+}
+extern "C" int64_t chm_debug_node_flag_words(const chm_batch* b, int pairs, int64_t* n_cleared) {
+  if (!b) return fail(CHM_E_ARG, "chm_debug_node_flag_words: batch is NULL");
+  if (pairs < 1 || pairs > b->P) return fail(CHM_E_ARG, "chm_debug_node_flag_words: pairs must be in [1, max_pairs]");
+  long np = 0;
+  const long n = node_flag_words(b, edge_plan(b, pairs), &np);
+  if (n_cleared) *n_cleared = n ? 2L * kMaxLayers + np : 0;
+  return n;
+}
+
+// The decoder's node-side launches alone (the node_* functions run_decoder calls, on the plan a decoder call with
+// `pairs` conditionings on this batch takes) on caller operands (tests/test_gpu_node_kernels.py). Every argument
+// check runs before the first HIP call, the batch-independent ones first, so a refused call needs no device. The
+// batch buffers a stage writes are filled with 0xff bytes (NaNs) first: an output the launch left out shows.
+extern "C" int chm_debug_node_stage(chm_batch* b, int pairs, int stage, int layer, const chm_debug_node_io* io,
+                                    void* stream) {
+  auto bad = [&](const char* field, const std::string& why) {
+    return fail(CHM_E_ARG, std::string("chm_debug_node_stage (stage ") + std::to_string(stage) + "): " + field + " " + why);
+  };
+  auto unsupported = [&](const std::string& why) {
+    return fail(CHM_E_UNSUPPORTED, std::string("chm_debug_node_stage (stage ") + std::to_string(stage) + "): " + why);
+  };
+  if (!io) return bad("io", "is NULL");
+  if (stage < 1 || stage > 4) return bad("stage", "must be in [1, 4]");
+  if (pairs < 1) return bad("pairs", "must be in [1, max_pairs]");
+  if (stage == 3 && layer < 0) return bad("layer", "must be in [0, num_layers)");
+  // the pointers each stage needs whatever the batch is
+  if (stage == 1) {
+    if (!io->d_temb) return bad("d_temb", "is NULL");
+    if (!io->d_cin) return bad("d_cin", "is NULL");
+    if (!io->d_t && io->tstride < 0) return bad("tstride", "must be >= 0");
+  } else if (stage == 2) {
+    if (!io->d_a) return bad("d_a", "is NULL");
+    if (!io->d_lat) return bad("d_lat", "is NULL");
+    if (!io->d_Hres) return bad("d_Hres", "is NULL");
+    if (!io->d_gbias) return bad("d_gbias", "is NULL");
+  } else if (stage == 3) {
+    if (!io->d_Hres) return bad("d_Hres", "is NULL");
+    if (!io->d_Hl) return bad("d_Hl", "is NULL");
+  } else {
+    if (!io->d_Hres) return bad("d_Hres", "is NULL");
+    if (!io->d_lat) return bad("d_lat", "is NULL");
+    if (!io->d_HO) return bad("d_HO", "is NULL");
+    if (!io->d_Hf) return bad("d_Hf", "is NULL");
+    if (!io->d_LAT) return bad("d_LAT", "is NULL");
+  }
+  if (stage == 2 || stage == 3)
+    if ((io->d_split == nullptr) != (io->d_exp == nullptr))
+      return bad(io->d_split ? "d_exp" : "d_split", "is NULL (the split rows and their exponents go together)");
+  if (!b) return bad("batch", "is NULL");
+  const chm_model* m = b->m;
+  if (pairs > b->P) return bad("pairs", "must be in [1, max_pairs]");
+  const int L = m->d.num_layers, X = m->d.text_dim, B = b->B, A = m->d.max_atoms;
+  if (stage == 3 && layer >= L) return bad("layer", "must be in [0, num_layers)");
+  const long N = b->N, R = (long)pairs * N, RS = (long)b->P * N;
+  const EdgePlan ep = edge_plan(b, pairs);
+  auto sized = [&](const void* p, int64_t n, long expect, const char* name, const char* shape) -> int {
+    if (p && n != expect)
+      return bad(name, "has " + std::to_string(n) + " elements, " + shape + " needs " + std::to_string(expect));
+    return CHM_OK;
+  };
+  int rc;
+  long n_flags = 0;
+  if (stage == 1) {
+    if (!m->film) return unsupported("the model has no FilmLayer (time_dim = text_dim = 0): no conditioning input");
+    if (io->d_t) {
+      if (io->n_t != 1) return bad("n_t", "must be 1 (one device int32)");
+      if (io->n_temb < TD || io->n_temb % TD) return bad("n_temb", "must be rows of time_dim = 128 (a table indexed by *d_t)");
+    } else if ((rc = sized(io->d_temb, io->n_temb, (long)(B - 1) * io->tstride + TD, "n_temb", "[B] rows tstride apart")))
+      return rc;
+    if (X > 0 && !io->d_text0) return bad("d_text0", "is NULL (text_dim > 0)");
+    if (X > 0 && pairs > 1 && !io->d_text1) return bad("d_text1", "is NULL (text_dim > 0, pairs = 2)");
+    if ((rc = sized(io->d_text0, io->n_text0, (long)B * X, "n_text0", "[B,text_dim]"))) return rc;
+    if ((rc = sized(io->d_text1, io->n_text1, (long)B * X, "n_text1", "[B,text_dim]"))) return rc;
+    if ((rc = sized(io->d_cin, io->n_cin, (long)pairs * B * (TD + X), "n_cin", "[pairs,B,time_dim+text_dim]"))) return rc;
+  } else if (stage == 2) {
+    if ((rc = sized(io->d_a, io->n_a, N, "n_a", "[N]"))) return rc;
+    if ((rc = sized(io->d_lat, io->n_lat, (long)B * 9, "n_lat", "[B,3,3]"))) return rc;
+    if ((rc = sized(io->d_Hres, io->n_Hres, R * H, "n_Hres", "[pairs,N,H]"))) return rc;
+    if ((rc = sized(io->d_gbias, io->n_gbias, (long)L * B * H, "n_gbias", "[L,B,H]"))) return rc;
+    if (io->d_rmax && !rmx_row(b, ep, RMX_H)) return bad("d_rmax", "is not written on this plan (split16 without node_ps only)");
+    if ((rc = sized(io->d_rmax, io->n_rmax, R, "n_rmax", "[pairs N]"))) return rc;
+    if (io->d_split && !ep.ps) return bad("d_split", "is not written on this plan (split16 with node_ps only)");
+    if ((rc = sized(io->d_split, io->n_split, R * 2 * H, "n_split", "[pairs N][H/16][hi 16 | lo 16]"))) return rc;
+    if ((rc = sized(io->d_exp, io->n_exp, R, "n_exp", "[pairs N]"))) return rc;
+    n_flags = node_flag_words(b, ep, nullptr);
+    if (io->d_flags && !n_flags) return bad("d_flags", "is not written on this plan (the pair grid only)");
+    if ((rc = sized(io->d_flags, io->n_flags, n_flags, "n_flags", "chm_debug_node_flag_words"))) return rc;
+  } else if (stage == 3) {
+    if (m->film && !io->d_Y) return bad("d_Y", "is NULL (the model has a FilmLayer)");
+    if (m->film && !io->d_cemb) return bad("d_cemb", "is NULL (the model has a FilmLayer)");
+    if ((rc = sized(io->d_Y, io->n_Y, R * H, "n_Y", "[pairs,N,H]"))) return rc;
+    if ((rc = sized(io->d_cemb, io->n_cemb, (long)pairs * B * 2 * H, "n_cemb", "[pairs,B,2H]"))) return rc;
+    if ((rc = sized(io->d_Hres, io->n_Hres, R * H, "n_Hres", "[pairs,N,H]"))) return rc;
+    if ((rc = sized(io->d_Hl, io->n_Hl, R * H, "n_Hl", "[pairs,N,H]"))) return rc;
+    if (io->d_rmax && !rmx_row(b, ep, 0)) return bad("d_rmax", "is not written on this plan (split16 without node_ps only)");
+    if ((rc = sized(io->d_rmax, io->n_rmax, 4 * R, "n_rmax", "[4][pairs N]"))) return rc;
+    if (io->d_split && !ep.ps) return bad("d_split", "is not written on this plan (split16 with node_ps only)");
+    if ((rc = sized(io->d_split, io->n_split, R * 2 * H, "n_split", "[pairs N][H/16][hi 16 | lo 16]"))) return rc;
+    if ((rc = sized(io->d_exp, io->n_exp, R, "n_exp", "[pairs N]"))) return rc;
+  } else {
+    if ((rc = sized(io->d_Hres, io->n_Hres, R * H, "n_Hres", "[pairs,N,H]"))) return rc;
+    if ((rc = sized(io->d_lat, io->n_lat, (long)B * 9, "n_lat", "[B,3,3]"))) return rc;
+    if ((rc = sized(io->d_HO, io->n_HO, R * HEADS_N, "n_HO", "[pairs N,128]"))) return rc;
+    if ((rc = sized(io->d_Hf, io->n_Hf, R * H, "n_Hf", "[pairs,N,H]"))) return rc;
+    if ((rc = sized(io->d_LAT, io->n_LAT, (long)pairs * B * 9, "n_LAT", "[pairs,B,3,3]"))) return rc;
+    if ((rc = sized(io->d_types, io->n_types, R * A, "n_types", "[pairs,N,max_atoms]"))) return rc;
+    if ((rc = sized(io->d_coords, io->n_coords, R * 3, "n_coords", "[pairs,N,3]"))) return rc;
+  }
+
+  hipStream_t s = (hipStream_t)stream;
+  const auto D2D = hipMemcpyDeviceToDevice;
+  const size_t f4 = sizeof(float);
+  if (stage == 1) {
+    HIPCHK(hipMemsetAsync(b->cin, 0xff, (size_t)b->P * B * (TD + X) * f4, s));
+    if ((rc = node_cond_in(b, pairs, io->d_temb, io->d_t ? 0 : io->tstride, io->d_t, io->d_text0, io->d_text1, s))) return rc;
+    HIPCHK(hipMemcpyAsync(io->d_cin, b->cin, (size_t)io->n_cin * f4, D2D, s));
+  } else if (stage == 2) {
+    HIPCHK(hipMemsetAsync(b->Hres, 0xff, (size_t)RS * H * f4, s));
+    HIPCHK(hipMemsetAsync(b->gbias, 0xff, (size_t)L * B * H * f4, s));
+    HIPCHK(hipMemsetAsync(b->rmx, 0xff, (size_t)4 * RS * f4, s));
+    if (ep.ps) {
+      HIPCHK(hipMemsetAsync(b->Hs, 0xff, (size_t)RS * H * 4, s));
+      HIPCHK(hipMemsetAsync(b->He, 0xff, (size_t)RS * sizeof(int), s));
+    }
+    const long nx = 2L * kMaxLayers;
+    if (io->d_flags) {
+      HIPCHK(hipMemcpyAsync(b->xbad, io->d_flags, nx * sizeof(unsigned), D2D, s));
+      HIPCHK(hipMemcpyAsync(b->psched, io->d_flags + nx, (n_flags - nx) * sizeof(unsigned), D2D, s));
+    }
+    if ((rc = node_embed(b, ep, pairs, io->d_a, io->d_lat, s))) return rc;
+    if ((rc = node_graph_bias_rest(b, io->d_lat, s))) return rc;
+    HIPCHK(hipMemcpyAsync(io->d_Hres, b->Hres, (size_t)R * H * f4, D2D, s));
+    HIPCHK(hipMemcpyAsync(io->d_gbias, b->gbias, (size_t)L * B * H * f4, D2D, s));
+    if (io->d_rmax) HIPCHK(hipMemcpyAsync(io->d_rmax, rmx_row(b, ep, RMX_H), (size_t)R * f4, D2D, s));
+    if (io->d_split) {
+      HIPCHK(hipMemcpyAsync(io->d_split, b->Hs, (size_t)R * H * 4, D2D, s));
+      HIPCHK(hipMemcpyAsync(io->d_exp, b->He, (size_t)R * sizeof(int), D2D, s));
+    }
+    if (io->d_flags) {
+      HIPCHK(hipMemcpyAsync(io->d_flags, b->xbad, nx * sizeof(unsigned), D2D, s));
+      HIPCHK(hipMemcpyAsync(io->d_flags + nx, b->psched, (n_flags - nx) * sizeof(unsigned), D2D, s));
+    }
+  } else if (stage == 3) {
+    if (m->film) {
+      HIPCHK(hipMemcpyAsync(b->Y, io->d_Y, (size_t)R * H * f4, D2D, s));
+      HIPCHK(hipMemcpyAsync(b->cemb, io->d_cemb, (size_t)pairs * B * 2 * H * f4, D2D, s));
+    }
+    HIPCHK(hipMemcpyAsync(b->Hres, io->d_Hres, (size_t)R * H * f4, D2D, s));
+    HIPCHK(hipMemsetAsync(b->Hl, 0xff, (size_t)RS * H * f4, s));
+    HIPCHK(hipMemsetAsync(b->rmx, 0xff, (size_t)4 * RS * f4, s));
+    if (ep.ps) {
+      HIPCHK(hipMemsetAsync(b->Hls, 0xff, (size_t)RS * H * 4, s));
+      HIPCHK(hipMemsetAsync(b->Hle, 0xff, (size_t)RS * sizeof(int), s));
+    }
+    if ((rc = node_film_ln(b, ep, pairs, layer, s))) return rc;
+    HIPCHK(hipMemcpyAsync(io->d_Hres, b->Hres, (size_t)R * H * f4, D2D, s));
+    HIPCHK(hipMemcpyAsync(io->d_Hl, b->Hl, (size_t)R * H * f4, D2D, s));
+    if (io->d_rmax)  // (the batch's rows are max_pairs N apart)
+      HIPCHK(hipMemcpy2DAsync(io->d_rmax, (size_t)R * f4, b->rmx, (size_t)RS * f4, (size_t)R * f4, 4, D2D, s));
+    if (io->d_split) {
+      HIPCHK(hipMemcpyAsync(io->d_split, b->Hls, (size_t)R * H * 4, D2D, s));
+      HIPCHK(hipMemcpyAsync(io->d_exp, b->Hle, (size_t)R * sizeof(int), D2D, s));
+    }
+  } else {
+    HIPCHK(hipMemcpyAsync(b->Hres, io->d_Hres, (size_t)R * H * f4, D2D, s));
+    HIPCHK(hipMemcpyAsync(b->HO, io->d_HO, (size_t)R * HEADS_N * f4, D2D, s));
+    HIPCHK(hipMemsetAsync(b->Hf, 0xff, (size_t)RS * H * f4, s));
+    HIPCHK(hipMemsetAsync(b->LAT, 0xff, (size_t)b->P * B * 9 * f4, s));
+    if ((rc = node_final_ln(b, pairs, s))) return rc;
+    if ((rc = node_graph_heads(b, pairs, io->d_lat, s))) return rc;
+    if (io->d_types || io->d_coords)
+      if ((rc = node_split_heads(b, pairs, io->d_types, io->d_coords, s))) return rc;
+    HIPCHK(hipMemcpyAsync(io->d_Hf, b->Hf, (size_t)R * H * f4, D2D, s));
+    HIPCHK(hipMemcpyAsync(io->d_LAT, b->LAT, (size_t)pairs * B * 9 * f4, D2D, s));
   }
   HIPCHK(hipStreamSynchronize(s));
   return CHM_OK;

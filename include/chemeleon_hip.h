@@ -490,6 +490,60 @@ int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac
                          int64_t n_pq, float* d_agg, int64_t n_agg, void* d_agg_split, int32_t* d_agg_exp,
                          void* stream);
 
+/* Test hook: the decoder's node-side launches alone (everything of a decoder call that is neither a GEMM nor the
+ * message path), by the very functions a decoder call runs them with (arguments built from the batch, its plan for
+ * `pairs` conditionings and the layer), on caller operands. Every pointer carries its ELEMENT count; a nullable
+ * output is skipped when NULL. fc and knn batches alike (these launches do not depend on the edges).
+ *   stage 1, the conditioning input (FiLM models only): d_temb + tstride (row g at d_temb + g tstride, n_temb =
+ *     (B-1) tstride + 128), or with d_t (one device int32, n_t = 1) d_temb a table of 128-wide rows read at row *d_t;
+ *     d_text0 / d_text1 [B,text_dim] (text_dim > 0; d_text1 for pairs = 2) -> d_cin [pairs,B,128+text_dim].
+ *   stage 2, the embedding launch and the per-graph terms: d_a [N] int64 (in [0, max_atoms): not checked), d_lat
+ *     [B,3,3] -> d_Hres [pairs,N,H]; d_gbias [L,B,H], all layers (the first 16 from the embedding launch, the rest
+ *     from the launches behind it); d_rmax [pairs N], max |row| (split16 batches without option node_ps); d_split
+ *     [pairs N][H/16][hi 16 | lo 16] fp16 (n_split = pairs N 2H) with d_exp [pairs N], the packed int8 exponents of
+ *     each row's four 128-column chunks (split16 with node_ps; both or neither); d_flags, IN and OUT, on a pair-grid
+ *     plan only: the words the launch clears, in the layout and count chm_debug_node_flag_words gives, copied into
+ *     the batch's words before the launch and back after it.
+ *   stage 3, FiLM + residual + LayerNorm of layer `layer`: d_Y [pairs,N,H] and d_cemb [pairs,B,2H] (FiLM models;
+ *     ignored without FilmLayer), d_Hres [pairs,N,H] IN and OUT, copied into the batch's buffers -> d_Hl [pairs,N,H];
+ *     d_rmax [4][pairs N], the four row-max arrays (RMX_H, RMX_HL, RMX_AGG, RMX_U); d_split / d_exp: Hl's split rows.
+ *   stage 4, the tail: d_Hres [pairs,N,H], d_lat, d_HO [pairs N,128] (the packed head rows) -> d_Hf [pairs,N,H] (the
+ *     final LayerNorm), d_LAT [pairs,B,3,3], d_types [pairs,N,max_atoms] and d_coords [pairs,N,3] (each nullable).
+ * The batch buffers a stage writes are filled with 0xff bytes before its launches. For tests only: it synchronises
+ * the stream. Every check (NULL pointers, stage, pairs, layer, element counts, an output the batch's plan does not
+ * write) returns CHM_E_ARG / CHM_E_UNSUPPORTED naming the field before the first HIP call, the ones that need no
+ * batch first, without a device. */
+typedef struct chm_debug_node_io {
+  const float* d_temb; int64_t n_temb;
+  const int32_t* d_t; int64_t n_t;
+  int32_t tstride, reserved;
+  const float* d_text0; int64_t n_text0;
+  const float* d_text1; int64_t n_text1;
+  float* d_cin; int64_t n_cin;
+  const int64_t* d_a; int64_t n_a;
+  const float* d_lat; int64_t n_lat;
+  const float* d_Y; int64_t n_Y;
+  const float* d_cemb; int64_t n_cemb;
+  const float* d_HO; int64_t n_HO;
+  float* d_Hres; int64_t n_Hres;
+  float* d_gbias; int64_t n_gbias;
+  float* d_Hl; int64_t n_Hl;
+  float* d_rmax; int64_t n_rmax;
+  void* d_split; int64_t n_split;
+  int32_t* d_exp; int64_t n_exp;
+  uint32_t* d_flags; int64_t n_flags;
+  float* d_Hf; int64_t n_Hf;
+  float* d_LAT; int64_t n_LAT;
+  float* d_types; int64_t n_types;
+  float* d_coords; int64_t n_coords;
+} chm_debug_node_io;
+int chm_debug_node_stage(chm_batch* b, int pairs, int stage, int layer, const chm_debug_node_io* io, void* stream);
+/* (host only, on a created batch) the words of stage 2's d_flags for `pairs` conditionings: 128 repair-request words,
+ * then the pair grid's per-layer flags, then the unused words up to the end of that buffer's allocation (a guard no
+ * launch may write). Returns their count (0: the plan clears nothing, d_flags is refused; negative: CHM_E_*) and in
+ * *n_cleared how many of them, from the front, the embedding launch zeroes. */
+int64_t chm_debug_node_flag_words(const chm_batch* b, int pairs, int64_t* n_cleared);
+
 /* Host-only test hook (no device): the row tiles edge layer 2 runs on for an fc batch of these
  * crystals (EdgeArgs::rtiles; DESIGN.md "Edge layer 2 on row tiles"). Returns the tile count R (or a
  * negative CHM_E_*); if out4 holds >= 4 R int32 it receives per tile {first node starting in the tile,

@@ -74,6 +74,18 @@ def test_null_handles_are_rejected():
     tt = _lib.chm_train_tables(100, x, x, x, 1.0, 1.0, 1.0, 1.0)
     assert lib.chm_debug_train_update(None, ctypes.byref(tt), *([x] * 8), 208, x, 6, x, 18, *([x] * 6), None) == -1
     assert b"chm_debug_train_update" in lib.chm_last_error() and b"batch" in lib.chm_last_error()
+    for stage, names in ((1, ("temb", "cin")), (2, ("a", "lat", "Hres", "gbias")), (3, ("Hres", "Hl")),
+                         (4, ("Hres", "lat", "HO", "Hf", "LAT"))):
+        nio = _lib.chm_debug_node_io()
+        assert lib.chm_debug_node_stage(None, 1, stage, 0, ctypes.byref(nio), None) == -1
+        assert b"chm_debug_node_stage" in lib.chm_last_error() and names[0].encode() in lib.chm_last_error()
+        for n in names:
+            setattr(nio, "d_" + n, x)
+        assert lib.chm_debug_node_stage(None, 1, stage, 0, ctypes.byref(nio), None) == -1
+        assert b"batch" in lib.chm_last_error()
+    assert lib.chm_debug_node_stage(None, 1, 2, 0, None, None) == -1 and b"io" in lib.chm_last_error()
+    assert lib.chm_debug_node_flag_words(None, 1, None) == -1
+    assert ctypes.sizeof(_lib.chm_debug_node_io) == 8 * (2 + 2 + 1 + 2 * 19)  # (the header's struct, no padding)
 
 
 def test_cpu_tensors_are_refused():
