@@ -152,6 +152,8 @@ SIGNATURES = {
     "chm_debug_gemm": (c_int, [ctypes.POINTER(chm_debug_gemm_args), c_void_p]),
     "chm_debug_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                      c_void_p, c_void_p, c_void_p]),
+    "chm_debug_knn_edge_layer": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                         c_void_p, c_i64, c_void_p]),
     "chm_debug_node_stage": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(chm_debug_node_io), c_void_p]),
     "chm_debug_node_flag_words": (c_i64, [c_void_p, c_int, ctypes.POINTER(c_i64)]),
     "chm_debug_layer_jobs": (c_i64, [c_i64, c_int, c_int, ctypes.POINTER(c_i64), c_i64]),

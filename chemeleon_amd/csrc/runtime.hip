@@ -2271,6 +2271,55 @@ extern "C" int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const fl
   return CHM_OK;
 }
 
+// The same for knn batches (tests/test_gpu_knn_kernels.py): the radius graph of the caller's coordinates and lattices
+// (knn_build), then edge_features and edge_block on it as run_decoder runs them. Every argument check runs before the
+// first HIP call, the batch-independent ones first. knn_build's own refusals (a node above 256 edges, a graph above
+// the batch capacity) are returned as they are: they are decided on the host before anything is placed.
+extern "C" int chm_debug_knn_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac, int64_t n_frac,
+                                        const float* d_lat, int64_t n_lat, const float* d_PQ, int64_t n_pq, float* d_agg,
+                                        int64_t n_agg, void* stream) {
+  auto bad = [&](const char* field, const std::string& why) {
+    return fail(CHM_E_ARG, std::string("chm_debug_knn_edge_layer: ") + field + " " + why);
+  };
+  if (!d_frac) return bad("d_frac", "is NULL");
+  if (!d_lat) return bad("d_lat", "is NULL");
+  if (!d_PQ) return bad("d_PQ", "is NULL");
+  if (!d_agg) return bad("d_agg", "is NULL");
+  if (pairs < 1) return bad("pairs", "must be in [1, max_pairs]");
+  if (layer < 0) return bad("layer", "must be in [0, num_layers)");
+  if (n_frac < 3 || n_frac % 3) return bad("n_frac", "must be 3 N, N >= 1");
+  if (n_lat < 9 || n_lat % 9) return bad("n_lat", "must be 9 B, B >= 1");
+  const int64_t Nc = n_frac / 3;
+  if (n_pq != (int64_t)pairs * Nc * 2 * H)
+    return bad("n_pq", "is " + std::to_string(n_pq) + ", [pairs, N, 2H] has " + std::to_string((int64_t)pairs * Nc * 2 * H));
+  if (n_agg != (int64_t)pairs * Nc * H)
+    return bad("n_agg", "is " + std::to_string(n_agg) + ", [pairs, N, H] has " + std::to_string((int64_t)pairs * Nc * H));
+  for (const void* p : {(const void*)d_frac, (const void*)d_lat, (const void*)d_PQ, (const void*)d_agg})
+    if ((uintptr_t)p % 16) return bad("operands", "must be 16-byte aligned");
+  if (!b) return bad("batch", "is NULL");
+  const chm_model* m = b->m;
+  if (!b->knn) return fail(CHM_E_UNSUPPORTED, "chm_debug_knn_edge_layer: batch is an fc batch (knn batches only)");
+  if (Nc != b->N) return bad("n_frac", "is " + std::to_string(n_frac) + ", the batch needs " + std::to_string(3 * b->N));
+  if (n_lat != (int64_t)9 * b->B)
+    return bad("n_lat", "is " + std::to_string(n_lat) + ", the batch needs " + std::to_string(9 * (int64_t)b->B));
+  if (pairs > b->P) return bad("pairs", "must be in [1, max_pairs]");
+  if (layer >= m->d.num_layers) return bad("layer", "must be in [0, num_layers)");
+
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = knn_build(b, d_frac, d_lat, s)) return rc;
+  const long N = b->N;
+  const EdgePlan ep = edge_plan(b, pairs);  // (after knn_build: the plan reads the call's E)
+  if (const int rc = edge_features(b, ep, d_frac, s)) return rc;
+  HIPCHK(hipMemcpyAsync(b->PQ, d_PQ, (size_t)n_pq * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (const int rc = clear_edge_flags(b, ep, s, true)) return rc;
+  if (ep.n16)  // (film_ln zeroes agg's row maxima for the layer's atomic maxima)
+    HIPCHK(hipMemsetAsync(b->rmx + RMX_AGG * (long)b->P * N, 0, (size_t)b->P * N * sizeof(float), s));
+  if (const int rc = edge_block(b, pairs, layer, ep, false, s)) return rc;
+  HIPCHK(hipMemcpyAsync(d_agg, b->agg, (size_t)n_agg * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return CHM_OK;
+}
+
 // The words the embedding launch clears on a pair-grid plan, as chm_debug_node_stage's d_flags holds them: xbad
 // [2 kMaxLayers], then the pair grid's per-layer flags [L 8 npx], then the unused words up to the end of that
 // buffer's 256-byte-rounded allocation (the guard: no launch may write them). 0: the plan clears nothing.

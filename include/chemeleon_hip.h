@@ -490,6 +490,17 @@ int chm_debug_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac
                          int64_t n_pq, float* d_agg, int64_t n_agg, void* d_agg_split, int32_t* d_agg_exp,
                          void* stream);
 
+/* Test hook: the same message path on a knn batch. Builds the radius graph of d_frac [N,3] / d_lat [B,3,3] as a
+ * decoder call does (the refusals of that build are returned unchanged: CHM_E_UNSUPPORTED for a node above 256
+ * edges or a graph above the batch's edge capacity), writes the features of its edges (frac_diff as built, no
+ * wrap), runs the layer's edge block on the node-aligned segment tiles of that graph and copies agg [pairs,N,H]
+ * out; a node without edges has an all-zero row. n_lat = 9 B. Every argument check runs before any HIP call
+ * (CHM_E_ARG / CHM_E_UNSUPPORTED naming the field, without a device); fc batches are refused. Synchronises the
+ * stream. */
+int chm_debug_knn_edge_layer(chm_batch* b, int pairs, int layer, const float* d_frac, int64_t n_frac,
+                             const float* d_lat, int64_t n_lat, const float* d_PQ, int64_t n_pq, float* d_agg,
+                             int64_t n_agg, void* stream);
+
 /* Test hook: the decoder's node-side launches alone (everything of a decoder call that is neither a GEMM nor the
  * message path), by the very functions a decoder call runs them with (arguments built from the batch, its plan for
  * `pairs` conditionings and the layer), on caller operands. Every pointer carries its ELEMENT count; a nullable

@@ -66,6 +66,10 @@ def test_null_handles_are_rejected():
     x = ctypes.c_void_p(0x10000)  # (never dereferenced: the NULL batch is refused before any HIP call)
     assert lib.chm_debug_edge_layer(None, 1, 0, x, 3, x, 1024, x, 512, None, None, None) == -1
     assert b"batch" in lib.chm_last_error()
+    assert lib.chm_debug_knn_edge_layer(None, 1, 0, x, 3, x, 9, x, 1024, x, 512, None) == -1
+    assert b"chm_debug_knn_edge_layer" in lib.chm_last_error() and b"batch" in lib.chm_last_error()
+    assert lib.chm_debug_knn_edge_layer(None, 1, 0, x, 3, x, 8, x, 1024, x, 512, None) == -1
+    assert b"n_lat" in lib.chm_last_error()
     sc = _lib.chm_schedule(100, 104, 128, 0, x, x, x, x)
     io.d_atom_types, io.d_frac, io.d_lattices = x, x, x
     assert lib.chm_debug_step_update(None, ctypes.byref(sc), 1, None, 2.0, ctypes.byref(io), 0, 0, 0, x, 208, x, 6, x,
