@@ -19,10 +19,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/chemeleon_hip.h"
+#include "chm_host.h"
 #include "cell_shared.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
 
 // Every product and sum is rounded on its own, in fp32 and in fp64, so that the record is the same expression on
 // every build (constrain.hip explains why the toolchain's __fmul_rn alone does not prevent contraction).
@@ -37,13 +35,7 @@ constexpr int kMaxPasses = 100;      // cap of the reduction
 constexpr int kMaxEntry = 32767;     // cap of |T|'s entries: products of two stay inside 2^31 and far inside fp64
 constexpr double kNiggliEps = 1.0e-5;  // times V^(2/3): the comparisons are between squared lengths
 
-int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(CHM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using chm::fail;
 
 struct CellArgs {
   const float* lat;

@@ -1,4 +1,5 @@
-// Internal declarations shared by kernels.hip and runtime.hip.
+// Kernel-facing internal declarations: the launchers of the kernel units and their argument structs, as the host
+// units call them (what the host units share among themselves is chm_host.h's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -19,9 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/chemeleon_hip.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
+#include "chm_host.h"
 
 // fp32 with every product and sum rounded on its own (screen.hip, constrain.hip): the fingerprint is the same
 // expression on every build
@@ -42,13 +40,7 @@ constexpr int kPairTile = 32;  // k_dedup_match: 32 x 32 pairs per block, one wo
 constexpr int kDimChunk = 64;  // fingerprint entries staged at a time
 constexpr int kLeadBlock = 64;  // k_dedup_lead: one wave
 
-int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(CHM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using chm::fail;
 
 // k_state_snapshot's clamp: a class outside [0, 103] is X
 __device__ inline int clamp_number(long a) { return (a >= 0 && a < kClasses) ? (int)a : 0; }

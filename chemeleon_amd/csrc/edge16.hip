@@ -923,7 +923,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16(EdgeArgs g) {
 
 // Edge layer 2 on 192-row tiles (3 row groups per wave: three quarters of a 256-row tile's MFMAs and epilogue):
 // the second launch of a mixed row tiling, whose 256-row tiles fill whole rounds of the CUs and whose short tiles
-// take the partial last round (runtime.hip short_row_tiles)
+// take the partial last round (batch.hip short_row_tiles)
 __global__ __launch_bounds__(512, 1) void k_edge16_short(EdgeArgs g) {
   edge16_tile<EPI_SEGMEAN, true, false, 3>(g, blockIdx.x, gridDim.x);
 }

@@ -12,9 +12,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "../../include/chemeleon_hip.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
+#include "chm_host.h"
 
 namespace {
 constexpr int kN = 624, kM = 397;
@@ -44,9 +42,9 @@ inline float temper_uniform(uint32_t y) {
 extern "C" int chm_mt19937_uniform(uint32_t* state, int32_t* left, int32_t* next, int64_t count, int64_t lo,
                                    int64_t hi, float* out) {
   if (!state || !left || !next || count < 0 || lo < 0 || hi < lo || hi > count || (hi > lo && !out))
-    return chm_fail_host(CHM_E_ARG, "chm_mt19937_uniform: NULL pointer or [lo, hi) outside [0, count)");
+    return chm::fail(CHM_E_ARG, "chm_mt19937_uniform: NULL pointer or [lo, hi) outside [0, count)");
   if (*left < 1 || *left > kN || *next < 0 || *next > kN || (*left > 1 && *next + *left != kN + 1))
-    return chm_fail_host(CHM_E_ARG, "chm_mt19937_uniform: engine position outside the MT19937 state");
+    return chm::fail(CHM_E_ARG, "chm_mt19937_uniform: engine position outside the MT19937 state");
   int l = *left, nx = *next;
   int64_t i = 0;
   while (i < count) {

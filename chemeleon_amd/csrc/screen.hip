@@ -19,9 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/chemeleon_hip.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
+#include "chm_host.h"
 
 // Distances are fp32 with every product and sum rounded on its own, each Cartesian component summed over
 // k = 0, 1, 2 in order, so that the record is the same expression on every build (constrain.hip explains why
@@ -36,13 +34,7 @@ constexpr int kTile = 256;     // atoms staged in LDS at a time
 constexpr int kMaxRange = 4;   // cap of the image range per axis
 constexpr int kNone = 0x7fffffff;
 
-int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(CHM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using chm::fail;
 
 // k_state_snapshot's clamp: a class outside [0, 103] is X
 __device__ inline int clamp_number(long a) { return (a >= 0 && a < kClasses) ? (int)a : 0; }

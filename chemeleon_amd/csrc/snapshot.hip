@@ -12,9 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/chemeleon_hip.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
+#include "chm_host.h"
 
 namespace {
 
@@ -23,13 +21,7 @@ constexpr int kWave = 64;      // one wavefront per crystal
 constexpr int kChunk = 1024;   // sort keys staged in LDS at a time (bytes)
 constexpr unsigned kPadKey = 0xffu;  // above every rank: never counted
 
-int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(CHM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using chm::fail;
 
 // the atomic number a structure gets for class a: the reference's clamp (classes above 103 -> 0); negative
 // classes, which the sampler never produces, also -> 0

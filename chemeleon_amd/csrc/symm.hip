@@ -19,10 +19,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/chemeleon_hip.h"
+#include "chm_host.h"
 #include "cell_shared.h"
-
-int chm_fail_host(int code, const char* msg);  // runtime.hip: sets chm_last_error()
 
 // Every product and sum is rounded on its own (as in cell.hip).
 #pragma clang fp contract(off)
@@ -35,13 +33,7 @@ constexpr int kBlock = 256;     // four waves per crystal
 constexpr int kMaxAtoms = 256;  // the LDS staging
 constexpr int kMaxOps = CHM_SYMM_MAX_OPS;
 
-int fail(int code, const std::string& msg) { return chm_fail_host(code, msg.c_str()); }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(CHM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using chm::fail;
 
 struct SymmArgs {
   const chm_cell_record* rec;

@@ -1,5 +1,5 @@
 """Cases and an independent reference of the radius-graph ("knn") edge path (csrc/knn.hip, knn_build in
-csrc/runtime.hip, the node-aligned segment tiles of edge layer 2), for tests/test_knn_cases.py on the CPU and
+csrc/decoder.hip, the node-aligned segment tiles of edge layer 2), for tests/test_knn_cases.py on the CPU and
 tests/test_gpu_knn_kernels.py on the GPU. A plain helper module: every input is seeded or exact.
 
 The reference (`graph`) is written from the definition in numpy float64 and Python integers; it shares no code

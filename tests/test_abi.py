@@ -188,6 +188,48 @@ def test_segment_mean_refuses_mis_sized_messages():
     torch.cuda.synchronize()
 
 
+# chm_model_set_option's whole surface: key -> None (every int64 is taken) or (lowest, highest, refusal text)
+_I64 = (-2**63, 2**63 - 1)
+OPTIONS = {
+    "node_ps": None, "edge_split": None, "edge_rows": None, "edge_layer": None, "edge_pairs": None,
+    "edge_pairs_layer": None, "edge_rows_short": None, "xcd_mask": None,
+    "edge_layer_repair": None, "edge_tail_timeout": None, "edge_tail_norepair": None, "edge_pairs_pq_global": None,
+    "edge_rows_nowait": None,
+    "edge_layer_dyn": (0, 2, b"edge_layer_dyn must be 0, 1 or 2"),
+    "edge_dyn_skip_xcd": (-1, 7, b"edge_dyn_skip_xcd must be in [-1, 7]"),
+    "edge_layer_min": (1, _I64[1], b"edge_layer_min must be >= 1"),
+    "edge_pool": (0, 100, b"edge_pool must be in [0, 100]"),
+    "edge_lag": (1, 1000, b"edge_lag must be in [1, 1000]"),
+}
+
+
+@pytest.mark.gpu
+def test_model_options_accept_their_ranges_and_refuse_the_rest():
+    """Every key of chm_model_set_option takes its lowest and its highest accepted value; a ranged key refuses the
+    value below and the value above with CHM_E_ARG and its own text; edge16 takes 1 only; an unknown key is named."""
+    m, _b = _gpu_batch([2], 1)
+    lib = _lib.load()
+    h = m.decoder.hip_model().handle
+
+    def set_option(key, value):
+        return lib.chm_model_set_option(h, key.encode(), value)
+
+    for key, rng in OPTIONS.items():
+        lo, hi = rng[:2] if rng else _I64
+        for v in (lo, hi):
+            assert set_option(key, v) == 0, (key, v, lib.chm_last_error())
+        for v in (lo - 1, hi + 1) if rng else ():
+            if _I64[0] <= v <= _I64[1]:
+                assert set_option(key, v) == -1, (key, v)
+                assert lib.chm_last_error() == rng[2], (key, v, lib.chm_last_error())
+    assert set_option("edge16", 1) == 0
+    assert set_option("edge16", 0) == -3
+    assert lib.chm_last_error() == b"edge16 = 0: the 32x32x16 edge kernels were removed"
+    assert set_option("edge_lagg", 1) == -1
+    assert lib.chm_last_error() == b"unknown option: edge_lagg"
+    assert lib.chm_model_set_option(h, None, 1) == -1 and lib.chm_model_set_option(None, b"edge_lag", 1) == -1
+
+
 @pytest.mark.gpu
 def test_d3pm_sample_refuses_out_of_range_indices(golden):
     """The round-4 k_d3pm clamped caller indices into a plausible wrong sample; now an out-of-range t or x_t

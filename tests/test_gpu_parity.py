@@ -310,7 +310,7 @@ def test_t1_step_512x40_math(model1000, golden, cn, math):
 def test_edge_tail_split_is_bit_identical(cn, nat):
     """When edge layer 1's 256x256 tiles leave a short partial round of the grid (64 x 40: 800 tiles
     on 256 CUs), the runtime runs that round in one grid with edge layer 2, whose segment tiles that
-    read its rows wait for them inside the grid (runtime.hip run_decoder, option 'edge_split';
+    read its rows wait for them inside the grid (decoder.hip edge_block, option 'edge_split';
     k_edge16_tail). Same tiles, same arithmetic: one reverse step must agree bit for bit with the
     one-launch-per-layer schedule. Shapes: partial rounds of 32, 14 and 6 tiles (ragged: segment
     tiles spanning crystals of 1-80 atoms wait on layer-1 tiles)."""
