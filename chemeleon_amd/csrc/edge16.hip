@@ -15,6 +15,10 @@
 // quarters of 24 with the next quarter's fragment reads between them, the tile's barrier before
 // the last quarter, and the next tile's A fragments read under that quarter.
 //
+// This K loop is written once, struct KLoop below: edge16_tile (row tiles, 4 or 3 row groups per wave) and pair_tile
+// (edge layer 1 on pairs, 2 row groups and a 128-row A stage) instantiate it and keep only their tile-index math,
+// waits, trace stamps and epilogues.
+//
 // Accumulators are C^T fragments: lane l holds edge row (l & 15) of each 16-row group and output
 // columns 16j + 4(l >> 4) .. +3 of each 16-column group j. Edge layer 1 stores S with the columns
 // of each 32-chunk permuted, 16a + 4g + r -> 8g + 4a + r (one 16-B store per plane), and W2's K
@@ -70,6 +74,10 @@ constexpr bool kPairAbl = CHM_PAIR_ABL;
 #endif
 constexpr bool kL2Sel = CHM_L2_SEL;
 
+// (named directly by the K loop: through a stored pointer its fragment addresses lose the no-wrap flags that fold
+// their constant parts into the ds_read offsets)
+extern __shared__ __attribute__((aligned(16))) char lds[];
+
 namespace {
 
 __device__ __forceinline__ f32x4 mfma16(const f16x8& a, const f16x8& b, const f32x4& c) {
@@ -107,6 +115,195 @@ __device__ __forceinline__ unsigned xcc_id() {
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
   return x & 7u;
 }
+
+// The split16 K loop of one wave, written once for the row tiles (edge16_tile: RG = 4 or 3 row groups per wave,
+// AM = 256 A rows staged per K-tile) and the pair tiles (pair_tile: RG = 2, AM = 128). LDS holds NSA A stages of
+// AM rows, then NSW W stages of 256 rows. UNI: the branch-free form (kLoopUni above).
+// A caller builds it where it declares its accumulators, then start(), first_reads(), tile<0>(t), tile<1>(t + 1) over
+// its K-tiles (the accumulator set per call), and waits for vmcnt(0) and a barrier before it reuses the LDS.
+template <int RG, int AM, bool UNI>
+struct KLoop {
+  static constexpr int A_LD = AM / 64;          // A global_load_lds per wave and K-tile, 8 rows each (W: 4)
+  static constexpr int A_STAGE = AM * ROW_B;    // bytes per A stage (W: OPND_B)
+  static constexpr int W_BASE = NSA * A_STAGE;  // the W stages follow the A stages
+  static_assert(W_BASE + NSW * OPND_B <= LDS_B, "LDS");
+  const char *Ablk, *Wblk;  // the tile's first A / W row at K-tile 0
+  int nk;                   // K-tiles (even)
+  unsigned aoff, woff, aodd, wodd, q8;
+  char *dstA, *dstW;
+  int wave, lane, ch0, ch1, fa, fw;
+  typedef f16x8 FragA[2][2][RG];  // [set][plane][row group]
+  typedef f16x8 FragW[2][2][2];   // [set][plane][column group of the quarter]
+  FragA& fA;  // (the caller's arrays)
+  FragW& fW;
+
+  // glds sources: wave w stages A rows (AM / 8) w .. and W rows 32 w .. 32 w + 31, 8 rows per instruction; lane ->
+  // row base + 8 q + (lane >> 3), LDS chunk lane & 7 holding line chunk (lane & 7) ^ swz(row), swz(row) =
+  // (row >> 1) & 7. A rows past the tile's last are read unclamped (F and S carry 256 rows of padding; those rows'
+  // results are never stored). rowB: bytes per split row (4 K).
+  __device__ __forceinline__ KLoop(FragA& fA_, FragW& fW_, const char* Ablk_, const char* Wblk_, long rowB, int nk_,
+                                   int wave_, int lane_)
+      : fA(fA_), fW(fW_), Ablk(Ablk_), Wblk(Wblk_), nk(nk_), wave(wave_), lane(lane_) {
+    const int ra0 = wave * (AM / 8) + (lane >> 3), rw0 = wave * 32 + (lane >> 3);
+    const unsigned ac16 = 16u * (unsigned)((lane & 7) ^ ((ra0 >> 1) & 7));
+    const unsigned wc16 = 16u * (unsigned)((lane & 7) ^ ((rw0 >> 1) & 7));
+    aoff = (unsigned)(ra0 * rowB) + ac16;
+    woff = (unsigned)(rw0 * rowB) + wc16;
+    q8 = (unsigned)(8 * rowB);
+    // (row + 8: its swizzle differs in bit 2, i.e. the source chunk moves by 64 bytes; the move is a 32-bit
+    // unsigned difference, so it is added to the offset BEFORE the pointer: offset + move never wraps)
+    aodd = (ac16 ^ 64u) - ac16;
+    wodd = (wc16 ^ 64u) - wc16;
+    dstA = lds + wave * (AM / 8) * ROW_B;
+    dstW = lds + wave * 32 * ROW_B + W_BASE;
+  }
+  // (UNI: past the end of K, a re-read of the last tile)
+  __device__ __forceinline__ void issueA(int t) {
+    const char* src = Ablk + (long)(t < nk ? t : nk - 1) * ROW_B;
+    char* d = dstA + (t % NSA) * A_STAGE;
+#pragma unroll
+    for (int q = 0; q < A_LD; ++q)
+      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (aoff + q * q8 + ((q & 1) ? aodd : 0u))),
+                                       (lds_void*)(d + q * 8 * ROW_B), 16, 0, 0);
+  }
+  __device__ __forceinline__ void issueW(int t) {
+    const char* src = Wblk + (long)(t < nk ? t : nk - 1) * ROW_B;
+    char* d = dstW + (t % NSW) * OPND_B;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (woff + q * q8 + ((q & 1) ? wodd : 0u))),
+                                       (lds_void*)(d + q * 8 * ROW_B), 16, 0, 0);
+  }
+  __device__ __forceinline__ void read_A(int set, int t) {
+    const char* SA = lds + (t % NSA) * A_STAGE + fa;
+#pragma unroll
+    for (int i = 0; i < RG; ++i) {
+      fA[set][0][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch0);
+      fA[set][1][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch1);
+    }
+  }
+  __device__ __forceinline__ void read_W(int set, int t, int qq) {
+    const char* SW = lds + W_BASE + (t % NSW) * OPND_B + fw + qq * 32 * ROW_B;
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      fW[set][0][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch0);
+      fW[set][1][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch1);
+    }
+  }
+  // one quarter: columns 32qq .. 32qq+31 of the wave, all RG row groups, three products
+  // (small terms first: w_lo a_hi, w_hi a_lo, then w_hi a_hi)
+  __device__ __forceinline__ void mfq(f32x4 (&acc)[RG][8], int aset, int wset, int qq) {
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][1][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][1][i], acc[i][2 * qq + jj]);
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
+  }
+  // quarter with NR fragment reads spread between its 6 RG MFMAs (one per two MFMAs)
+  template <int NR>
+  __device__ __forceinline__ void sched_reads() {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 6 * RG - 2 * NR, 0);
+  }
+
+  // prologue (issue order W0 A0 A1 W1 A2): tile 0 has landed when A1, W1 and A2 remain
+  // fragment of row r (16-row group base + l16), k-chunk g4 of plane p: logical chunk 4p + g4 at physical chunk
+  // (4p + g4) ^ swz(r); swz depends on l16 only (group bases are multiples of 16)
+  __device__ __forceinline__ void start() {
+    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, g4 = lane >> 4;
+    const int swz = (l16 >> 1) & 7;
+    ch0 = 16 * (g4 ^ swz);
+    ch1 = 16 * ((4 + g4) ^ swz);
+    fa = (wm * 16 * RG + l16) * ROW_B;
+    fw = (wn * 128 + l16) * ROW_B;
+    issueW(0);
+    issueA(0);
+    issueA(1);
+    issueW(1);
+    issueA(2);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * A_LD + 4) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  }
+  __device__ __forceinline__ void first_reads() {
+    read_A(0, 0);
+    read_W(0, 0, 0);
+  }
+
+  // tile t: A fragments in set a = t & 1, W quarter fragments alternating sets 0, 1, 0, 1; the 6 RG MFMAs of each
+  // quarter with the next quarter's fragment reads between them, the tile's barrier before the last quarter, and
+  // the next tile's operand loads and A fragment reads under that quarter. before(t) runs ahead of the quarters,
+  // after_barrier(t) behind the tile's operand loads (block-uniform branches there keep the loop's shape, which
+  // keeps the register allocation spill-free).
+  template <int a, class Before, class After>
+  __device__ __forceinline__ void tile(f32x4 (&acc)[RG][8], int t, Before& before, After& after_barrier) {
+    before(t);
+    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): A_t and W_t quarter 0 are in
+    __builtin_amdgcn_s_setprio(1);
+    read_W(1, t, 1);
+    mfq(acc, a, 0, 0);
+    sched_reads<4>();
+    __builtin_amdgcn_s_setprio(0);
+    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_setprio(1);
+    read_W(0, t, 2);
+    mfq(acc, a, 1, 1);
+    sched_reads<4>();
+    __builtin_amdgcn_s_setprio(0);
+    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_setprio(1);
+    read_W(1, t, 3);
+    mfq(acc, a, 0, 2);
+    sched_reads<4>();
+    __builtin_amdgcn_s_setprio(0);
+    // this wave is done reading tile t; this thread's part of tile t+1 has landed (only A(t+2) may
+    // still be in flight; near the end everything is waited for); after the barrier everyone's
+    // has, and tile t's stages are free
+    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (!kAblVm) {
+      if (UNI || t < nk - 2)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD) : "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    if (!kAblBar) __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_setprio(1);
+    if ((UNI || t + 2 < nk) && !kAblLd) issueW(t + 2);
+    if ((UNI || t + 3 < nk) && !kAblLd) issueA(t + 3);
+    after_barrier(t);
+    read_A(a ^ 1, t + 1);  // past the end: reads stale stages (never used)
+    read_W(0, t + 1, 0);
+    mfq(acc, a, 1, 3);
+    // 6 RG MFMAs and 2 RG + 4 fragment reads: one MFMA beside each operand load, one beside each fragment read
+    // while they last, then the rest of either alone (RG = 4: 4 MFMAs, 3: none, 2: 2 reads)
+    constexpr int NM = 6 * RG, NV = 4 + A_LD, ND = 2 * RG + 4, NDP = ND < NM - NV ? ND : NM - NV;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
+      __builtin_amdgcn_sched_group_barrier(0x010, 1, 1);
+    }
+#pragma unroll
+    for (int k = 0; k < NDP; ++k) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
+    }
+    if constexpr (NM - NV > NDP) __builtin_amdgcn_sched_group_barrier(0x008, NM - NV - NDP, 1);
+    if constexpr (ND > NDP) __builtin_amdgcn_sched_group_barrier(0x100, ND - NDP, 1);
+    __builtin_amdgcn_s_setprio(0);
+  }
+};
 
 }  // namespace
 
@@ -148,6 +345,8 @@ __host__ __device__ inline LayerJob layer_job(long b, long R, int P, int D) {
 template <int EPI, bool ASC, bool ONE = false, int RG = 4>
 __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb, long bid_in = -1, int tid_in = -1) {
   static_assert(RG == 4 || (RG == 3 && EPI == EPI_SEGMEAN && !ONE), "short row tiles: edge layer 2's own launch");
+  // (the node-list fallback below places tile t at row 256 t, which a mixed tiling's short tiles are not)
+  static_assert(RG == 4 || kSegTable, "short row tiles read their node list from the host-built table");
   constexpr int RW = 16 * RG;  // rows per wave row (wm)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   // (tid_in >= 0: the persistent kernel's opaque copy of threadIdx.x, so its loop does not hoist the
@@ -201,40 +400,15 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
     }
   };
 
-  // ---- glds sources: wave w stages rows 32w..32w+31 of both operands, 8 rows per
-  // instruction; lane -> row 32w + 8q + (lane >> 3), LDS chunk lane & 7 holding line chunk
-  // (lane & 7) ^ swz(row), swz(row) = (row >> 1) & 7. A rows past nrows are read unclamped (F and S
-  // carry 256 rows of padding; those rows' results are never stored).
+  // ---- the K loop's operands: the tile's A rows and W rows (KLoop stages 256 A rows per K-tile: the rows past a
+  // short tile are read, never used)
   const char* Ab = reinterpret_cast<const char*>(g.A);
   const char* Wb = reinterpret_cast<const char*>(g.W);
   const long rowB = (long)K * 4;
   // (dbg 32768 / 65536, profiling: layer-1 / layer-2 tiles read their A rows from the first 16 row tiles,
   // which stay L2-resident: the launch time without the A operand's HBM misses)
   const bool a_l2 = (EPI == EPI_EDGE && (g.dbg & 32768)) || (EPI == EPI_SEGMEAN && (g.dbg & 65536));
-  const char* Ablk = Ab + (a_l2 ? row0 % (16 * BM) : row0) * rowB;
-  const char* Wblk = Wb + (long)n0 * rowB;
-  const int lr0 = wave * 32 + (lane >> 3);
-  const unsigned lc16 = 16u * (unsigned)((lane & 7) ^ ((lr0 >> 1) & 7));
-  const unsigned lc16x = lc16 ^ 64u;
-  const unsigned woff = (unsigned)(lr0 * rowB) + lc16;
-  const unsigned wq = (unsigned)(8 * rowB);
-  char* dst = lds + wave * 32 * ROW_B;
-  auto issueA = [&](int t) __attribute__((always_inline)) {
-    const char* src = Ablk + (long)(t < nk ? t : nk - 1) * ROW_B;
-    char* d = dst + (t % NSA) * OPND_B;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (woff + q * wq + ((q & 1) ? (lc16x - lc16) : 0u))),
-                                       (lds_void*)(d + q * 8 * ROW_B), 16, 0, 0);
-  };
-  auto issueW = [&](int t) __attribute__((always_inline)) {
-    const char* src = Wblk + (long)(t < nk ? t : nk - 1) * ROW_B;
-    char* d = dst + W_RING + (t % NSW) * OPND_B;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (woff + q * wq + ((q & 1) ? (lc16x - lc16) : 0u))),
-                                       (lds_void*)(d + q * 8 * ROW_B), 16, 0, 0);
-  };
+
 
   if (EPI == EPI_EDGE && g.zero_flags && vb == 0 && tid < g.nzero) g.zero_flags[tid] = 0u;  // (for the next grid)
   if (EPI == EPI_EDGE && g.flags && (g.dbg & 8192))  // (tests: the segment tiles' waits time out)
@@ -315,45 +489,11 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // fragment of row r (16-row group base + l16), k-chunk g4 of plane p: logical chunk 4p + g4 at
-  // physical chunk (4p + g4) ^ swz(r); swz depends on l16 only (group bases are multiples of 16)
-  const int swz = (l16 >> 1) & 7;
-  const int ch0 = 16 * (g4 ^ swz), ch1 = 16 * ((4 + g4) ^ swz);
-  const int fa = (wm * RW + l16) * ROW_B, fw = (wn * 128 + l16) * ROW_B;
-  f16x8 fA[2][2][RG];  // [set][plane][row group]
-  f16x8 fW[2][2][2];  // [set][plane][column group of the quarter]
-  auto read_A = [&](int set, int t) __attribute__((always_inline)) {
-    const char* SA = lds + (t % NSA) * OPND_B + fa;
-#pragma unroll
-    for (int i = 0; i < RG; ++i) {
-      fA[set][0][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch0);
-      fA[set][1][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch1);
-    }
-  };
-  auto read_W = [&](int set, int t, int qq) __attribute__((always_inline)) {
-    const char* SW = lds + W_RING + (t % NSW) * OPND_B + fw + qq * 32 * ROW_B;
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      fW[set][0][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch0);
-      fW[set][1][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch1);
-    }
-  };
-  // one quarter: columns 32qq .. 32qq+31 of the wave, all RG row groups, three products
-  // (small terms first: w_lo a_hi, w_hi a_lo, then w_hi a_hi)
-  auto mfq = [&](int aset, int wset, int qq) __attribute__((always_inline)) {
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][1][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][1][i], acc[i][2 * qq + jj]);
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < RG; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
-  };
+  // (not branch-free for the directed layer-1 tiles, whose last K-tiles stage P / Q rows into the A ring)
+  typedef KLoop<RG, BM, kLoopUni && EPI != EPI_EDGE> KL;
+  typename KL::FragA fA;
+  typename KL::FragW fW;
+  KL kl(fA, fW, Ab + (a_l2 ? row0 % (16 * BM) : row0) * rowB, Wb + (long)n0 * rowB, rowB, nk, wave, lane);
   auto rescale = [&](int t) __attribute__((always_inline)) {
     if (ASC && t > 0 && (t * BK) % CHUNK == 0) {
       const int c = (t * BK) / CHUNK;
@@ -367,28 +507,8 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
       }
     }
   };
-  // quarter with n fragment reads spread between its 6 RG MFMAs (one per two MFMAs)
-  auto sched_reads = [&](auto NR) __attribute__((always_inline)) {
-    constexpr int nr = decltype(NR)::value;
-#pragma unroll
-    for (int k = 0; k < nr; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 6 * RG - 2 * nr, 0);
-  };
-
-  // prologue (issue order W0 A0 A1 W1 A2): tile 0 landed when 12 glds remain
-  issueW(0);
-  issueA(0);
-  issueA(1);
-  issueW(1);
-  issueA(2);
-  asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  read_A(0, 0);
-  read_W(0, 0, 0);
+  kl.start();
+  kl.first_reads();
 
   // EPI_EDGE: the epilogue's P / Q rows are staged during the last K-tiles (their latency then hides
   // under those MFMAs) when the ring layout allows it (nk % 6 == 0: tiles nk-3, nk-2 sit in A stages
@@ -419,71 +539,17 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
     }
   };
 
-  // tile t: A fragments in set a = t & 1, W quarter fragments alternating sets 0, 1, 0, 1.
-  // Pre-staging blocks (EPI_EDGE) skip the loads past the end of K and stage conditioning 0's P / Q
-  // rows after the barrier of tile nk-2, conditioning 1's after that of nk-1 (block-uniform
-  // branches; the loop keeps its shape, which keeps the register allocation spill-free).
-  auto tile = [&](int t, auto CUR) __attribute__((always_inline)) {
-    constexpr int a = decltype(CUR)::value;
-    rescale(t);
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): A_t and W_t quarter 0 are in
-    __builtin_amdgcn_s_setprio(1);
-    read_W(1, t, 1);
-    mfq(a, 0, 0);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_setprio(1);
-    read_W(0, t, 2);
-    mfq(a, 1, 1);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_setprio(1);
-    read_W(1, t, 3);
-    mfq(a, 0, 2);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    // this wave is done reading tile t; this thread's part of tile t+1 has landed (only A(t+2) may
-    // still be in flight; near the end everything is waited for); after the barrier everyone's
-    // has, and tile t's stages are free
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    constexpr bool uni = kLoopUni && EPI != EPI_EDGE;
-    if (!kAblVm) {
-      if (uni || t < nk - 2)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (!kAblBar) __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_setprio(1);
-    if ((uni || t + 2 < nk) && !kAblLd) issueW(t + 2);  // (uni: past the end of K, a re-read of the last tile)
-    if ((uni || t + 3 < nk) && !kAblLd) issueA(t + 3);
+  // Pre-staging blocks (EPI_EDGE) stage conditioning 0's P / Q rows after the barrier of tile nk-2,
+  // conditioning 1's after that of nk-1
+  auto stage_pre = [&](int t) __attribute__((always_inline)) {
     if (EPI == EPI_EDGE && pre) {
       if (t == nk - 2) stage_rows(0, 0);
       if (t == nk - 1 && g.npairs > 1) stage_rows(1, PRE_ROW1);
     }
-    read_A(a ^ 1, t + 1);  // past the end: reads stale stages (never used)
-    read_W(0, t + 1, 0);
-    mfq(a, 1, 3);
-    // 6 RG MFMAs: 8 beside the operand loads, 2 RG + 4 beside the fragment reads, the rest (RG = 4: 4) alone
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-      __builtin_amdgcn_sched_group_barrier(0x010, 1, 1);
-    }
-#pragma unroll
-    for (int k = 0; k < 2 * RG + 4; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-    }
-    if constexpr (4 * RG > 12) __builtin_amdgcn_sched_group_barrier(0x008, 4 * RG - 12, 1);
-    __builtin_amdgcn_s_setprio(0);
   };
   for (int t = 0; t < nk; t += 2) {  // nk = K / 32 is even (K = 512, 768)
-    tile(t, std::integral_constant<int, 0>{});
-    tile(t + 1, std::integral_constant<int, 1>{});
+    kl.template tile<0>(acc, t, rescale, stage_pre);
+    kl.template tile<1>(acc, t + 1, rescale, stage_pre);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (staged P / Q rows) land before the LDS is reused
   __syncthreads();
@@ -925,7 +991,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16(EdgeArgs g) {
 // the second launch of a mixed row tiling, whose 256-row tiles fill whole rounds of the CUs and whose short tiles
 // take the partial last round (batch.hip short_row_tiles)
 __global__ __launch_bounds__(512, 1) void k_edge16_short(EdgeArgs g) {
-  edge16_tile<EPI_SEGMEAN, true, false, 3>(g, blockIdx.x, gridDim.x);
+  if constexpr (kSegTable) edge16_tile<EPI_SEGMEAN, true, false, 3>(g, blockIdx.x, gridDim.x);
 }
 
 // Edge layer 1's partial last round and edge layer 2 in one grid: blocks [0, nb1) are layer-1 tiles
@@ -1150,11 +1216,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16_repair(EdgeArgs g, long nvb, 
 // Tile: 128 pairs x 256 columns, 8 waves of 32 pairs x 128 columns (two accumulator sets of 64 registers:
 // the budget of edge16_tile's one set of 128); split rows, swizzle, MFMA and C^T layout as edge16_tile.
 namespace {
-constexpr int PBM = 128;                 // pairs per tile
-constexpr int P_NSA = 3, P_NSW = 2;      // ring depths: A (streamed), W (L2-resident)
-constexpr int P_OPA = PBM * ROW_B;       // 16 KB per A stage
-constexpr int P_WRING = P_NSA * P_OPA;   // W stages follow the A stages (32 KB each)
-static_assert(P_WRING + P_NSW * OPND_B <= LDS_B, "LDS");
+constexpr int PBM = 128;  // pairs per tile: 16 KB per A stage of the K loop
 static_assert(PBM == kPairRows, "pair tile rows (host tables)");
 // the epilogue's staged P / Q rows: per node [P 256 | Q 256 | 8 pad] floats of this column tile (a pitch of 8
 // dwords mod 64 banks: the 16 lanes of a ds_read_b128 group, rows of consecutive nodes, hit distinct banks)
@@ -1173,39 +1235,14 @@ __device__ __forceinline__ void pair_tile(const EdgeArgs& g, long bid, int tid_i
   const long nrows = g.Mp - row0 < PBM ? g.Mp - row0 : PBM;
   constexpr int nk = FD / BK;        // 24: K-tiles [0, 12) sine features, [12, 24) cosine
   constexpr int rowB = FD * 4;       // one split row of K = 768
-  // glds: wave w stages A rows 16 w .. 16 w + 15 (2 instructions) and W rows 32 w .. 32 w + 31 (4); lane ->
-  // row base + 8 q + (lane >> 3), LDS chunk lane & 7 holding line chunk (lane & 7) ^ ((row >> 1) & 7)
   // (traced A/B builds only, dbg 32768: the pair tiles read their F rows from the first 16 pair tiles, which stay
   // L2-resident: the tile time without F's HBM reads; wrong results)
   const long arow0 = (kGridTrace && (g.dbg & 32768)) ? row0 % (16 * PBM) : row0;
-  const char* Ablk = reinterpret_cast<const char*>(g.A) + arow0 * rowB;
-  const char* Wblk = reinterpret_cast<const char*>(g.W) + (long)n0 * rowB;
-  const int ra0 = wave * 16 + (lane >> 3), rw0 = wave * 32 + (lane >> 3);
-  const unsigned aoff = (unsigned)(ra0 * rowB) + 16u * (unsigned)((lane & 7) ^ ((ra0 >> 1) & 7));
-  const unsigned woff = (unsigned)(rw0 * rowB) + 16u * (unsigned)((lane & 7) ^ ((rw0 >> 1) & 7));
-  const unsigned q8 = (unsigned)(8 * rowB);
-  // (row + 8: its swizzle differs in bit 2, i.e. the source chunk moves by 64 bytes; the move is a 32-bit
-  // unsigned difference, so it is added to the offset BEFORE the pointer: offset + move never wraps)
-  const unsigned aodd = (((unsigned)(lane & 7) ^ (unsigned)((ra0 >> 1) & 7)) ^ 4u) * 16u - 16u * (unsigned)((lane & 7) ^ ((ra0 >> 1) & 7));
-  const unsigned wodd = (((unsigned)(lane & 7) ^ (unsigned)((rw0 >> 1) & 7)) ^ 4u) * 16u - 16u * (unsigned)((lane & 7) ^ ((rw0 >> 1) & 7));
-  char* dstA = lds + wave * 16 * ROW_B;
-  char* dstW = lds + P_WRING + wave * 32 * ROW_B;
-  auto issueA = [&](int t) __attribute__((always_inline)) {
-    const char* src = Ablk + (long)(t < nk ? t : nk - 1) * ROW_B;
-    char* d = dstA + (t % P_NSA) * P_OPA;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (aoff + q * q8 + (q & 1 ? aodd : 0u))), (lds_void*)(d + q * 8 * ROW_B),
-                                       16, 0, 0);
-  };
-  auto issueW = [&](int t) __attribute__((always_inline)) {
-    const char* src = Wblk + (long)(t < nk ? t : nk - 1) * ROW_B;
-    char* d = dstW + (t % P_NSW) * OPND_B;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src + (woff + q * q8 + (q & 1 ? wodd : 0u))), (lds_void*)(d + q * 8 * ROW_B),
-                                       16, 0, 0);
-  };
+  typedef KLoop<2, PBM, kLoopUni> KL;
+  KL::FragA fA;
+  KL::FragW fW;
+  KL kl(fA, fW, reinterpret_cast<const char*>(g.A) + arow0 * rowB,
+                             reinterpret_cast<const char*>(g.W) + (long)n0 * rowB, rowB, nk, wave, lane);
 
   f32x4 accV[2][8], accU[2][8];
 #pragma unroll
@@ -1213,126 +1250,21 @@ __device__ __forceinline__ void pair_tile(const EdgeArgs& g, long bid, int tid_i
 #pragma unroll
     for (int j = 0; j < 8; ++j) accV[i][j] = accU[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int swz = (l16 >> 1) & 7;
-  const int ch0 = 16 * (g4 ^ swz), ch1 = 16 * ((4 + g4) ^ swz);
-  const int fa = (wm * 32 + l16) * ROW_B, fw = (wn * 128 + l16) * ROW_B;
-  f16x8 fA[2][2][2];  // [set][plane][row group]
-  f16x8 fW[2][2][2];  // [set][plane][column group of the quarter]
-  auto read_A = [&](int set, int t) __attribute__((always_inline)) {
-    const char* SA = lds + (t % P_NSA) * P_OPA + fa;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      fA[set][0][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch0);
-      fA[set][1][i] = *reinterpret_cast<const f16x8*>(SA + i * 16 * ROW_B + ch1);
-    }
-  };
-  auto read_W = [&](int set, int t, int qq) __attribute__((always_inline)) {
-    const char* SW = lds + P_WRING + (t % P_NSW) * OPND_B + fw + qq * 32 * ROW_B;
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) {
-      fW[set][0][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch0);
-      fW[set][1][jj] = *reinterpret_cast<const f16x8*>(SW + jj * 16 * ROW_B + ch1);
-    }
-  };
-  // one quarter (32 columns of the wave, both row groups, three products: small terms first)
-  auto mfq = [&](f32x4 (&acc)[2][8], int aset, int wset, int qq) __attribute__((always_inline)) {
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][1][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][1][i], acc[i][2 * qq + jj]);
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) acc[i][2 * qq + jj] = mfma16(fW[wset][0][jj], fA[aset][0][i], acc[i][2 * qq + jj]);
-  };
-  auto sched_reads = [&](auto NR) __attribute__((always_inline)) {  // NR fragment reads among 12 MFMAs
-    constexpr int nr = decltype(NR)::value;
-#pragma unroll
-    for (int k = 0; k < nr; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 12 - 2 * nr, 0);
-  };
-
   // the node range of the epilogue's P / Q rows (one load, issued ahead of the operand stream: in by tile 0)
   int2 pqn = {0, 0};
   if (g.pnode) pqn = g.pnode[row0 / PBM];
-  // prologue (issue order W0 A0 A1 W1 A2): tile 0 has landed when 8 glds remain (A1 2, W1 4, A2 2)
-  issueW(0);
-  issueA(0);
-  issueA(1);
-  issueW(1);
-  issueA(2);
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  kl.start();
   // (block-uniform: SGPRs across the main loop)
   const int q_lo = __builtin_amdgcn_readfirstlane(pqn.x), q_n = __builtin_amdgcn_readfirstlane(pqn.y);
-  read_A(0, 0);
-  read_W(0, 0, 0);
-
-  auto tile = [&](f32x4 (&acc)[2][8], int t, auto CUR) __attribute__((always_inline)) {
-    constexpr int a = decltype(CUR)::value;
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): A_t and W_t quarter 0 are in
-    __builtin_amdgcn_s_setprio(1);
-    read_W(1, t, 1);
-    mfq(acc, a, 0, 0);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_setprio(1);
-    read_W(0, t, 2);
-    mfq(acc, a, 1, 1);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_setprio(1);
-    read_W(1, t, 3);
-    mfq(acc, a, 0, 2);
-    sched_reads(std::integral_constant<int, 4>{});
-    __builtin_amdgcn_s_setprio(0);
-    // this wave is done reading tile t; this thread's part of tile t+1 has landed (only A(t+2) may still
-    // be in flight: 2 glds; near the end everything is waited for); after the barrier everyone's has
-    if (!kAblLgkm) __builtin_amdgcn_s_waitcnt(0xC07F);
-    if (!kAblVm) {
-      if (kLoopUni || t < nk - 2)
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (!kAblBar) __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_setprio(1);
-    if ((kLoopUni || t + 2 < nk) && !kAblLd) issueW(t + 2);
-    if ((kLoopUni || t + 3 < nk) && !kAblLd) issueA(t + 3);
-    read_A(a ^ 1, t + 1);  // past the end: reads stale stages (never used)
-    read_W(0, t + 1, 0);
-    mfq(acc, a, 1, 3);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-      __builtin_amdgcn_sched_group_barrier(0x010, 1, 1);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x100, 2, 1);
-    __builtin_amdgcn_s_setprio(0);
-  };
+  kl.first_reads();
+  auto none = [](int) __attribute__((always_inline)) {};
   for (int t = 0; t < nk / 2; t += 2) {  // the sine half of K into V
-    tile(accV, t, std::integral_constant<int, 0>{});
-    tile(accV, t + 1, std::integral_constant<int, 1>{});
+    kl.tile<0>(accV, t, none, none);
+    kl.tile<1>(accV, t + 1, none, none);
   }
   for (int t = nk / 2; t < nk; t += 2) {  // the cosine half into U
-    tile(accU, t, std::integral_constant<int, 0>{});
-    tile(accU, t + 1, std::integral_constant<int, 1>{});
+    kl.tile<0>(accU, t, none, none);
+    kl.tile<1>(accU, t + 1, none, none);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1669,14 +1601,30 @@ __global__ __launch_bounds__(512, 1) void k_edge16_pairs_grid(EdgeArgs g1, EdgeA
   }
 }
 
+// a layer-2 EdgeArgs on uniform tiles (no mixed tiling): operands, epilogue buffers, and on row tiles the cross-tile
+// exchange buffers and enough 256-row tiles for E rows
+static bool l2_uniform_ok(const EdgeArgs& g) {
+  return g.N == H && g.K % CHUNK == 0 && g.K / CHUNK <= 4 && g.agg && g.bias && g.aexp && g.node_n && g.A && g.W &&
+         g.wscale && !g.rt_first && !g.rt_count && !g.rt_h && !g.rt_e0 &&
+         (!g.rtiles || (g.sbuf && g.msgbuf && g.rcnt && (long)g.ntiles * BM >= g.E));
+}
+// The repair pair behind a one-grid launch (both exit at once unless the grid raised its repair request): the
+// launcher's own first repair kernel on repair_dim() blocks, then repair_layer2 recomputes every layer-2 tile of r2
+// without intra-grid waits, counted as event ev.
+static dim3 repair_dim(int repair_grid) { return dim3((unsigned)(repair_grid > 0 ? repair_grid : 256)); }
+static hipError_t repair_layer2(const EdgeArgs& r2, int repair_grid, int ev, hipStream_t s) {
+  const long nb2 = (long)r2.ntiles * r2.npairs * (r2.N / BN);
+  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), repair_dim(repair_grid), dim3(512), LDS_B, s, r2, nb2,
+                     (unsigned*)nullptr, 0L, (unsigned*)nullptr, 0L, ev);
+  return hipGetLastError();
+}
+
 hipError_t edge_gemm16_pairs_layer(const EdgeArgs& g1, const EdgeArgs& g2, const PairSched& ps, int repair_grid,
                                    hipStream_t s) {
   if (g1.N != H || g1.K != FD || !g1.A || !g1.W || !g1.wscale || !g1.S || !g1.sexp || !g1.PQ || !g1.pi || !g1.pj ||
       !g1.pe || g1.Mp < 1 || g1.npairs != g2.npairs || g1.E < g1.Mp || !g1.xbad || g1.xbad != g2.xbad)
     return hipErrorInvalidValue;
-  if (g2.N != H || g2.K % CHUNK || g2.K / CHUNK > 4 || !g2.rtiles || !g2.sbuf || !g2.msgbuf || !g2.rcnt || !g2.agg ||
-      !g2.bias || !g2.aexp || !g2.node_n || !g2.A || !g2.W || !g2.wscale || g2.flags || g2.lflags ||
-      (long)g2.ntiles != ps.R || (long)g2.ntiles * BM < g2.E || g2.rt_first || g2.rt_count || g2.rt_h || g2.rt_e0)
+  if (!l2_uniform_ok(g2) || !g2.rtiles || g2.flags || g2.lflags || (long)g2.ntiles != ps.R)
     return hipErrorInvalidValue;  // (uniform 256-row tiles only)
   if (!ps.jobs || !ps.pflag || ps.jstride < 1 || ps.npx < 1) return hipErrorInvalidValue;
   if (hipError_t e = edge16_init(); e != hipSuccess) return e;
@@ -1686,15 +1634,10 @@ hipError_t edge_gemm16_pairs_layer(const EdgeArgs& g1, const EdgeArgs& g2, const
   // the repair launches (exit at once unless a wait timed out or saw another XCD): clear layer 2's agg row
   // maxima and row-tile counters and recompute every pair tile, then every layer-2 tile (two launches; r5: the
   // clearing and the pair tiles were two launches, 4.5 us more per layer when nothing is repaired)
-  const unsigned rg = (unsigned)(repair_grid > 0 ? repair_grid : 256);
-  EdgeArgs r1 = g1, r2 = g2;
   const long nb1 = (g1.Mp + PBM - 1) / PBM * (H / BN);
-  hipLaunchKernelGGL(k_edge16_pairs_repair, dim3(rg), dim3(512), LDS_B, s, r1, nb1, g2.agg_max,
+  hipLaunchKernelGGL(k_edge16_pairs_repair, repair_dim(repair_grid), dim3(512), LDS_B, s, g1, nb1, g2.agg_max,
                      g2.agg_max ? (long)g2.npairs * g2.nnodes : 0L, g2.rcnt, g2.rcnt ? (long)g2.npairs * g2.ntiles * 8 : 0L);
-  const long nb2 = (long)g2.ntiles * g2.npairs * (g2.N / BN);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), dim3(rg), dim3(512), LDS_B, s, r2, nb2, (unsigned*)nullptr,
-                     0L, (unsigned*)nullptr, 0L, (int)EV_LAYER_REPAIR);
-  return hipGetLastError();
+  return repair_layer2(g2, repair_grid, EV_LAYER_REPAIR, s);
 }
 
 static hipError_t edge16_init_once() {
@@ -1733,10 +1676,7 @@ hipError_t edge_gemm16_tail(const EdgeArgs& g1, const EdgeArgs& g2, int repair_g
       !g1.flags || g1.flags != g2.flags || g1.flag_row0 != g1.row_base || g2.flag_row0 != g1.row_base ||
       !g2.xbad)
     return hipErrorInvalidValue;
-  if (g2.N != H || g2.K % CHUNK || g2.K / CHUNK > 4 || !g2.tiles || g2.ntiles < 1 || !g2.agg || !g2.bias ||
-      !g2.aexp || !g2.node_n || !g2.A || !g2.W || !g2.wscale || g2.rt_first || g2.rt_count || g2.rt_h || g2.rt_e0 ||
-      (g2.rtiles && (!g2.sbuf || !g2.msgbuf || !g2.rcnt || (long)g2.ntiles * BM < g2.E)))
-    return hipErrorInvalidValue;  // (uniform tiles only)
+  if (!l2_uniform_ok(g2) || !g2.tiles || g2.ntiles < 1) return hipErrorInvalidValue;  // (uniform tiles only)
   if (hipError_t e = edge16_init(); e != hipSuccess) return e;
   const long nt1 = ((g1.M - g1.row_base + BM - 1) / BM) * (g1.N / BN);
   const long nb1 = (nt1 + 7) / 8 * 8;
@@ -1750,12 +1690,9 @@ hipError_t edge_gemm16_tail(const EdgeArgs& g1, const EdgeArgs& g2, int repair_g
   EdgeArgs r1 = g1, r2 = g2;
   r1.flags = r2.flags = nullptr;
   r1.xbad = g2.xbad;
-  const unsigned rg = (unsigned)(repair_grid > 0 ? repair_grid : 256);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), dim3(rg), dim3(512), LDS_B, s, r1, 0L, g2.agg_max,
-                     g2.agg_max ? (long)g2.npairs * g2.nnodes : 0L, (unsigned*)nullptr, 0L, -1);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), dim3(rg), dim3(512), LDS_B, s, r2, nt2, (unsigned*)nullptr,
-                     0L, (unsigned*)nullptr, 0L, (int)EV_TAIL_REPAIR);
-  return hipGetLastError();
+  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), repair_dim(repair_grid), dim3(512), LDS_B, s, r1, 0L,
+                     g2.agg_max, g2.agg_max ? (long)g2.npairs * g2.nnodes : 0L, (unsigned*)nullptr, 0L, -1);
+  return repair_layer2(r2, repair_grid, EV_TAIL_REPAIR, s);
 }
 
 long edge16_layer_blocks(long R, int P) { return 8 * ((R + 7) / 8) * (2 + 2L * P); }
@@ -1785,10 +1722,8 @@ hipError_t edge_gemm16_layer(const EdgeArgs& g1, const EdgeArgs& g2, int lag, in
       !g1.n2g || !g1.A || !g1.W || !g1.wscale || g1.npairs > 2 || g1.row_base != 0 || g1.flags || !g1.lflags ||
       !g1.xbad || g1.xbad != g2.xbad)
     return hipErrorInvalidValue;
-  if (g2.N != H || g2.K % CHUNK || g2.K / CHUNK > 4 || !g2.rtiles || !g2.sbuf || !g2.msgbuf || !g2.rcnt || !g2.agg ||
-      !g2.bias || !g2.aexp || !g2.node_n || !g2.A || !g2.W || !g2.wscale || g2.flags || g2.lflags != g1.lflags ||
-      g2.npairs != g1.npairs || (long)g2.ntiles * BM < g2.E || (long)g2.ntiles * BM - g2.E >= BM || g1.M != g1.E ||
-      lag < 1 || g2.rt_first || g2.rt_count || g2.rt_h || g2.rt_e0)
+  if (!l2_uniform_ok(g2) || !g2.rtiles || g2.flags || g2.lflags != g1.lflags || g2.npairs != g1.npairs ||
+      (long)g2.ntiles * BM - g2.E >= BM || g1.M != g1.E || lag < 1)
     return hipErrorInvalidValue;  // (uniform 256-row tiles only)
   if (hipError_t e = edge16_init(); e != hipSuccess) return e;
   const long R = g2.ntiles;
@@ -1806,13 +1741,10 @@ hipError_t edge_gemm16_layer(const EdgeArgs& g1, const EdgeArgs& g2, int lag, in
   // the repair pair (exits at once unless a layer-2 tile flagged another XCD's layer-1 tile)
   EdgeArgs r1 = g1, r2 = g2;
   r1.lflags = r2.lflags = nullptr;
-  const long nb1 = ((g1.M + BM - 1) / BM) * (g1.N / BN), nb2 = (long)g2.ntiles * g2.npairs * (g2.N / BN);
-  const unsigned rg = (unsigned)(repair_grid > 0 ? repair_grid : 256);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), dim3(rg), dim3(512), LDS_B, s, r1, nb1, g2.agg_max,
-                     (long)g2.npairs * g2.nnodes, g1.lflags, R, -1, g2.rcnt, (long)g2.npairs * R * 8);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), dim3(rg), dim3(512), LDS_B, s, r2, nb2, (unsigned*)nullptr, 0L,
-                     (unsigned*)nullptr, 0L, (int)EV_LAYER_REPAIR);
-  return hipGetLastError();
+  const long nb1 = ((g1.M + BM - 1) / BM) * (g1.N / BN);
+  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), repair_dim(repair_grid), dim3(512), LDS_B, s, r1, nb1,
+                     g2.agg_max, (long)g2.npairs * g2.nnodes, g1.lflags, R, -1, g2.rcnt, (long)g2.npairs * R * 8);
+  return repair_layer2(r2, repair_grid, EV_LAYER_REPAIR, s);
 }
 
 hipError_t edge_gemm16(const EdgeArgs& g, int epi, hipStream_t s) {
@@ -1827,7 +1759,9 @@ hipError_t edge_gemm16(const EdgeArgs& g, int epi, hipStream_t s) {
     if (g.rtiles) {
       if (!g.sbuf || !g.msgbuf || !g.rcnt) return hipErrorInvalidValue;
       if (g.rt_first || g.rt_count || g.rt_h || g.rt_e0) {
-        // one launch of a mixed tiling: tiles [rt_first, rt_first + rt_count) of ntiles, each with at least one row
+        // one launch of a mixed tiling: tiles [rt_first, rt_first + rt_count) of ntiles, each with at least one row;
+        // their node lists come from the host-built table only (the device-side fallback assumes tile t at row 256 t)
+        if (!kSegTable || !g.rinfo || !g.rinfo_n) return hipErrorInvalidValue;
         nt = g.rt_count;
         if ((g.rt_h != 0 && g.rt_h != BM && g.rt_h != kShortRows) || g.rt_first < 0 || nt < 1 ||
             g.rt_first + nt > g.ntiles || g.rt_e0 < 0 || g.rt_e0 + (nt - 1) * (g.rt_h ? g.rt_h : BM) >= g.E)
