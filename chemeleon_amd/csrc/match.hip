@@ -1,0 +1,530 @@
+// Matching finished structures against reference structures on the device (chm_match_*, include/chemeleon_hip.h):
+// per crystal the integer lattice mappings M that carry the scaled reduced cell of the sample onto the reduced cell
+// of its reference within ltol / angle_tol, and for each of them the origin shifts t_j that put an atom of the
+// rarest species onto the reference's first atom of that species; a candidate (M, t_j) survives when every
+// reference atom's nearest sample atom of its type is within stol l and no sample atom is taken twice. The
+// survivor with the smallest rms displacement (mean removed) is the record (test_structure_matching of the
+// reference's scripts/evaluate.py). One 64-byte record per crystal and, if asked, the winner's atom pairing. The
+// plan (chm_match) is independent of chm_model / chm_batch: node offsets of both lists and ref_of, uploaded once.
+//
+// One 256-thread block per crystal. The reduced coordinates and types of the sample and of its reference (16 bytes
+// per atom, at most 256 atoms each) and the accepted mappings (at most 256 candidate indices, appended in ascending
+// order pass by pass) are staged in LDS. The candidates (M, t_j) are spread over the block, one thread each, with a
+// 256-bit "taken" set per thread in LDS. The winner is a 64-bit integer minimum in LDS over (rms bits, mapping
+// position, anchor position), every count an integer add, so the record does not depend on any order.
+#include <hip/hip_runtime.h>
+
+#include <limits.h>
+#include <math.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "chm_host.h"
+#include "cell_shared.h"
+
+// Every product and sum is rounded on its own (as in cell.hip).
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace chm_cellshared;
+
+constexpr int kBlock = 256;     // four waves per crystal
+constexpr int kMaxAtoms = 256;  // the LDS staging
+constexpr int kMaxMaps = CHM_MATCH_MAX_MAPPINGS;
+constexpr int kNoCell = CHM_CELL_NOT_REDUCED | CHM_CELL_DEGENERATE | CHM_CELL_NONFINITE;
+
+using chm::fail;
+
+struct MatchArgs {
+  const chm_cell_record* rec;   // [B] of the samples
+  const long long* types;
+  const float* x;
+  const float* lat;
+  const int* off;               // [B + 1]
+  const chm_cell_record* rrec;  // [R] of the references
+  const long long* rtypes;
+  const float* rx;
+  const float* rlat;
+  const int* roff;              // [R + 1]
+  const int* ref_of;            // [B]
+  float ltol, stol, angle_tol;
+  int4* out;                    // [B] records of 64 bytes
+  int* perm;                    // NULL or [N]
+};
+
+struct __align__(16) Atom {
+  float x[3];  // in the reduced basis, [0, 1)
+  int type;
+};
+
+// the rows of M A, entries (m0 a0 + m1 a1) + m2 a2
+__device__ inline void rows_of(const int* M, const float* A, float* out) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      out[3 * i + k] = ((float)M[3 * i] * A[k] + (float)M[3 * i + 1] * A[3 + k]) + (float)M[3 * i + 2] * A[6 + k];
+}
+
+// G(A): the six distinct entries 00, 11, 22, 01, 02, 12
+__device__ inline void gram(const float* A, float* g) {
+  g[0] = dot3(A, A), g[1] = dot3(A + 3, A + 3), g[2] = dot3(A + 6, A + 6);
+  g[3] = dot3(A, A + 3), g[4] = dot3(A, A + 6), g[5] = dot3(A + 3, A + 6);
+}
+
+// |d|^2 under the metric g (gram's order): (u0 d0 + u1 d1) + u2 d2, u_k = (d0 G[0][k] + d1 G[1][k]) + d2 G[2][k]
+__device__ inline float norm2(const float* g, const float* d) {
+  const float u0 = (d[0] * g[0] + d[1] * g[3]) + d[2] * g[4];
+  const float u1 = (d[0] * g[3] + d[1] * g[1]) + d[2] * g[5];
+  const float u2 = (d[0] * g[4] + d[1] * g[5]) + d[2] * g[2];
+  return (u0 * d[0] + u1 * d[1]) + u2 * d[2];
+}
+
+// Is candidate idx a unimodular M whose M sL has every row length within ltol (relative) and every inter-row angle
+// within atol (degrees) of the reference cell's (lr, ar of cell_metric)?
+__device__ inline bool mapping_accepted(int idx, const float* sL, const float* lr, const float* ar, float ltol, float atol) {
+  int M[9], det, tr;
+  decode_candidate(idx, M, &det, &tr);
+  if (det != 1 && det != -1) return false;
+  float A[9];
+  rows_of(M, sL, A);
+  const float m0 = sqrtf(dot3(A, A)), m1 = sqrtf(dot3(A + 3, A + 3)), m2 = sqrtf(dot3(A + 6, A + 6));
+  bool acc = fabsf(m0 / lr[0] - 1.f) <= ltol && fabsf(m1 / lr[1] - 1.f) <= ltol && fabsf(m2 / lr[2] - 1.f) <= ltol;
+  if (acc)
+    acc = fabsf(angle_deg(A + 3, A + 6, m1, m2) - ar[0]) <= atol && fabsf(angle_deg(A, A + 6, m0, m2) - ar[1]) <= atol &&
+          fabsf(angle_deg(A, A + 3, m0, m1) - ar[2]) <= atol;
+  return acc;
+}
+
+// Minv = det(M) adj(M) as floats (entries within +-2), and the metric 0.5 (G(M sL) + gr) of mapping idx
+__device__ inline void mapping_frame(int idx, const float* sL, const float* gr, float* Minv, float* g) {
+  int M[9], det, tr;
+  decode_candidate(idx, M, &det, &tr);
+  Minv[0] = (float)(det * (M[4] * M[8] - M[5] * M[7]));
+  Minv[1] = (float)(det * (M[2] * M[7] - M[1] * M[8]));
+  Minv[2] = (float)(det * (M[1] * M[5] - M[2] * M[4]));
+  Minv[3] = (float)(det * (M[5] * M[6] - M[3] * M[8]));
+  Minv[4] = (float)(det * (M[0] * M[8] - M[2] * M[6]));
+  Minv[5] = (float)(det * (M[2] * M[3] - M[0] * M[5]));
+  Minv[6] = (float)(det * (M[3] * M[7] - M[4] * M[6]));
+  Minv[7] = (float)(det * (M[1] * M[6] - M[0] * M[7]));
+  Minv[8] = (float)(det * (M[0] * M[4] - M[1] * M[3]));
+  float A[9], gm[6];
+  rows_of(M, sL, A);
+  gram(A, gm);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) g[q] = 0.5f * (gm[q] + gr[q]);
+}
+
+// x'' = frac(x' Minv)
+__device__ inline void mapped(const float* Minv, const float* x, float* out) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float y = (x[0] * Minv[k] + x[1] * Minv[3 + k]) + x[2] * Minv[6 + k];
+    float f = y - floorf(y);
+    if (f >= 1.0f) f = 0.0f;
+    out[k] = f;
+  }
+}
+
+// The sample atom of b's type nearest to reference atom b under (Minv, t, g): its index (-1 if none), |D|^2 and D.
+__device__ inline int nearest(const Atom* s_s, int n, const Atom b, const float* Minv, const float* t, const float* g,
+                              float* best, float* D) {
+  int bi = -1;
+  *best = INFINITY;
+  for (int i = 0; i < n; ++i) {
+    const Atom a = s_s[i];
+    if (a.type != b.type) continue;
+    float xm[3], d[3];
+    mapped(Minv, a.x, xm);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      d[k] = (xm[k] - t[k]) - b.x[k];
+      d[k] -= rintf(d[k]);
+    }
+    const float q = norm2(g, d);
+    if (q < *best) {
+      *best = q, bi = i;
+      D[0] = d[0], D[1] = d[1], D[2] = d[2];
+    }
+  }
+  return bi;
+}
+
+__device__ inline double det3(const float* L) {
+  const double l[9] = {L[0], L[1], L[2], L[3], L[4], L[5], L[6], L[7], L[8]};
+  return (l[0] * (l[4] * l[8] - l[5] * l[7]) - l[1] * (l[3] * l[8] - l[5] * l[6])) + l[2] * (l[3] * l[7] - l[4] * l[6]);
+}
+
+// LDS integers of the block
+enum { I_COMP = 0, I_MINCNT, I_PTYPE, I_PREF, I_VOLOK, I_NSURV, I_COUNT };
+// LDS floats of the block
+enum { F_SCALE = 0, F_ELL, F_MAXD, F_COUNT };
+
+// Block g (four waves) = crystal g.
+__global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
+  __shared__ Atom s_s[kMaxAtoms];  // the sample
+  __shared__ Atom s_r[kMaxAtoms];  // its reference
+  __shared__ int s_map[kMaxMaps];  // accepted candidate indices, ascending
+  __shared__ int s_piv[kMaxAtoms];  // the sample's atoms of the anchor species in node order
+  __shared__ unsigned s_taken[8 * kBlock];  // word w of thread t at [w * kBlock + t]
+  __shared__ float s_Ls[9], s_Lr[9], s_f[F_COUNT];
+  __shared__ int s_i[I_COUNT], s_wcnt[kBlock / 64];
+  __shared__ unsigned long long s_best;
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = p.off[g], n = p.off[g + 1] - n0;  // (1 <= n <= kMaxAtoms: chm_match_create)
+  const int r = p.ref_of[g];                       // (-1 <= r < R: chm_match_create)
+  int4* oi = p.out + 4 * (long)g;
+  // (r, n, nr and everything read from the cell records are the same in every thread: the branches on them are uniform)
+  if (r < 0) {
+    if (p.perm && tid < n) p.perm[(long)n0 + tid] = -1;
+    if (tid == 0) {
+      oi[0] = make_int4(0, 0, 0, 0);
+      oi[1] = make_int4(-1, -1, 0, 0);
+      oi[2] = make_int4(0, 0, CHM_MATCH_NO_REFERENCE, -1);
+      oi[3] = make_int4(0, 0, 0, 0);
+    }
+    return;
+  }
+  const int m0 = p.roff[r], nr = p.roff[r + 1] - m0;
+  const chm_cell_record* rec = p.rec + g;
+  const chm_cell_record* rrec = p.rrec + r;
+  int flags = 0;
+  if ((rec->flags & kNoCell) || (rrec->flags & kNoCell)) flags |= CHM_MATCH_NO_LATTICE;
+  if (n != nr) flags |= CHM_MATCH_SIZE;
+  int Ts[9], Tr[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) Ts[q] = rec->transform[q], Tr[q] = rrec->transform[q];
+
+  if (tid < 9) {
+    s_Ls[tid] = reduced_entry(Ts, p.lat + (long)g * 9, tid);
+    s_Lr[tid] = reduced_entry(Tr, p.rlat + (long)r * 9, tid);
+  }
+  if (tid < n) {
+    double adj[9];
+    adjugate(Ts, adj);
+    reduced_frac(adj, p.x + 3 * ((long)n0 + tid), s_s[tid].x);
+    s_s[tid].type = (int)p.types[(long)n0 + tid];
+  }
+  if (tid < nr) {
+    double adj[9];
+    adjugate(Tr, adj);
+    reduced_frac(adj, p.rx + 3 * ((long)m0 + tid), s_r[tid].x);
+    s_r[tid].type = (int)p.rtypes[(long)m0 + tid];
+  }
+  if (tid < I_COUNT) s_i[tid] = (tid == I_MINCNT || tid == I_PTYPE || tid == I_PREF) ? INT_MAX : 0;
+  if (tid < F_COUNT) s_f[tid] = 0.f;
+  if (tid == 0) s_best = ~0ull;
+  __syncthreads();
+
+  // ---- composition, and the anchor species: the one with the fewest atoms (ties: the smallest type)
+  int n_piv = 0, pref = 0;
+  if (n == nr) {
+    const int my = tid < n ? s_s[tid].type : 0;
+    const int myr = tid < n ? s_r[tid].type : 0;
+    int cnt_r = 0;
+    if (tid < n) {
+      int cs = 0, cr = 0;
+      for (int q = 0; q < n; ++q) cs += s_s[q].type == my, cr += s_r[q].type == my, cnt_r += s_r[q].type == myr;
+      if (cs != cr) s_i[I_COMP] = 1;
+      atomicMin(&s_i[I_MINCNT], cnt_r);
+    }
+    __syncthreads();
+    n_piv = s_i[I_MINCNT];
+    if (s_i[I_COMP]) flags |= CHM_MATCH_COMPOSITION;
+    if (tid < n && cnt_r == n_piv) atomicMin(&s_i[I_PTYPE], myr);
+    __syncthreads();
+    const int ptype = s_i[I_PTYPE];
+    if (tid < n && myr == ptype) atomicMin(&s_i[I_PREF], tid);
+    if (tid < n && my == ptype) {
+      int rank = 0;
+      for (int q = 0; q < tid; ++q) rank += s_s[q].type == ptype;
+      s_piv[rank] = tid;  // (rank < n_piv when the compositions are equal; < n always)
+    }
+    __syncthreads();
+    pref = s_i[I_PREF];
+  }
+
+  // ---- scale and l: fp64 on one lane, rounded once
+  float Ls[9], Lr[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) Ls[q] = s_Ls[q], Lr[q] = s_Lr[q];
+  if (!(flags & CHM_MATCH_NO_LATTICE)) {
+    if (tid == 0) {
+      const double vs = fabs(det3(Ls)), vr = fabs(det3(Lr));
+      const bool ok = vs > 0.0 && vr > 0.0 && vs < INFINITY && vr < INFINITY;
+      if (ok) {
+        s_f[F_SCALE] = (float)cbrt(vr / vs);
+        s_f[F_ELL] = (float)cbrt(vr / (double)nr);
+      }
+      s_i[I_VOLOK] = ok;
+    }
+    __syncthreads();
+    if (!s_i[I_VOLOK]) flags |= CHM_MATCH_NO_LATTICE;  // (uniform: from LDS behind a barrier)
+  }
+  const float scale = s_f[F_SCALE], ell = s_f[F_ELL];
+  const float c = p.stol * ell, c2 = c * c;
+
+  // ---- thin cells: one image per component is exact only while 2 c < the smallest plane spacing of Lr
+  if (flags == 0) {
+    const float c0[3] = {Lr[4] * Lr[8] - Lr[5] * Lr[7], Lr[5] * Lr[6] - Lr[3] * Lr[8], Lr[3] * Lr[7] - Lr[4] * Lr[6]};
+    const float c1[3] = {Lr[7] * Lr[2] - Lr[8] * Lr[1], Lr[8] * Lr[0] - Lr[6] * Lr[2], Lr[6] * Lr[1] - Lr[7] * Lr[0]};
+    const float c2v[3] = {Lr[1] * Lr[5] - Lr[2] * Lr[4], Lr[2] * Lr[3] - Lr[0] * Lr[5], Lr[0] * Lr[4] - Lr[1] * Lr[3]};
+    const float vol = fabsf(dot3(Lr, c0));
+    const float d0 = vol / sqrtf(dot3(c0, c0)), d1 = vol / sqrtf(dot3(c1, c1)), d2 = vol / sqrtf(dot3(c2v, c2v));
+    if (!(2.0f * c < fminf(fminf(d0, d1), d2))) flags |= CHM_MATCH_THIN;
+  }
+  const bool search = flags == 0;
+
+  // ---- the lattice mappings, appended in ascending candidate order pass by pass
+  float sL[9], gr[6];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) sL[q] = scale * Ls[q];
+  gram(Lr, gr);
+  int n_maps = 0;
+  if (search) {
+    float lr[3], ar[3];
+    cell_metric(Lr, lr, ar);
+    for (int first = 0; first < kCandidates; first += kBlock) {  // (every thread takes every pass: the ballot is whole)
+      const int idx = first + tid;
+      const bool acc = idx < kCandidates && mapping_accepted(idx, sL, lr, ar, p.ltol, p.angle_tol);
+      const unsigned long long b = __ballot(acc);
+      if (lane == 0) s_wcnt[wave] = __popcll(b);
+      __syncthreads();
+      int before = 0, all = 0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) {
+        const int cw = s_wcnt[w];
+        before += w < wave ? cw : 0;
+        all += cw;
+      }
+      const int slot = n_maps + before + __popcll(b & ((1ull << lane) - 1ull));
+      if (acc && slot < kMaxMaps) s_map[slot] = idx;
+      n_maps += all;
+      __syncthreads();  // (s_wcnt is rewritten in the next pass; s_map is read after the last)
+    }
+    if (n_maps > kMaxMaps) flags |= CHM_MATCH_MANY_MAPPINGS;
+  }
+  const int used = n_maps < kMaxMaps ? n_maps : kMaxMaps;
+
+  // ---- the candidates (M, t_j), one per thread
+  const int total = search ? used * n_piv : 0;  // (<= 256 * 256)
+  unsigned long long mine = ~0ull;
+  float mine_maxd = 0.f;
+  for (int cand = tid; cand < total; cand += kBlock) {
+    const int w = cand / n_piv, jj = cand - w * n_piv;
+    float Minv[9], gm[6], t[3];
+    mapping_frame(s_map[w], sL, gr, Minv, gm);
+    {
+      float xj[3];
+      mapped(Minv, s_s[s_piv[jj]].x, xj);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = xj[k] - s_r[pref].x[k];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s_taken[q * kBlock + tid] = 0u;
+    float sum[3] = {0.f, 0.f, 0.f};
+    bool ok = true;
+    for (int k = 0; k < n && ok; ++k) {
+      float best, D[3];
+      const int bi = nearest(s_s, n, s_r[k], Minv, t, gm, &best, D);
+      if (!(best <= c2)) {  // (also bi < 0 and NaN)
+        ok = false;
+      } else {
+        const unsigned bit = 1u << (bi & 31);
+        const unsigned word = s_taken[(bi >> 5) * kBlock + tid];
+        if (word & bit) {
+          ok = false;
+        } else {
+          s_taken[(bi >> 5) * kBlock + tid] = word | bit;
+          sum[0] += D[0], sum[1] += D[1], sum[2] += D[2];
+        }
+      }
+    }
+    if (!ok) continue;
+    atomicAdd(&s_i[I_NSURV], 1);
+    const float fn = (float)n;
+    const float mean[3] = {sum[0] / fn, sum[1] / fn, sum[2] / fn};
+    float sumq = 0.f, maxq = 0.f;
+    for (int k = 0; k < n; ++k) {
+      float best, D[3];
+      (void)nearest(s_s, n, s_r[k], Minv, t, gm, &best, D);
+      const float e[3] = {D[0] - mean[0], D[1] - mean[1], D[2] - mean[2]};
+      const float q = norm2(gm, e);
+      sumq += q;
+      maxq = fmaxf(maxq, q);
+    }
+    const float rms = sqrtf(sumq / fn) / ell;
+    if (rms <= p.stol) {  // (rms >= 0 or -0: its bits with the sign cleared order as the values do)
+      const unsigned long long key =
+          ((unsigned long long)(__float_as_uint(rms) & 0x7fffffffu) << 32) | ((unsigned long long)w << 8) | (unsigned long long)jj;
+      if (key < mine) mine = key, mine_maxd = sqrtf(maxq);
+    }
+  }
+  if (mine != ~0ull) atomicMin(&s_best, mine);
+  __syncthreads();
+  const unsigned long long best_key = s_best;
+  const bool matched = best_key != ~0ull;
+  if (matched && mine == best_key) s_f[F_MAXD] = mine_maxd;  // (one thread: the key names its candidate)
+  const int win_w = (int)((best_key >> 8) & 0xffu), win_jj = (int)(best_key & 0xffu);
+
+  // ---- the winner's pairing, recomputed: reference atom k -> its sample atom
+  if (p.perm) {
+    int partner = -1;
+    if (matched && tid < n) {
+      float Minv[9], gm[6], t[3], xj[3], best, D[3];
+      mapping_frame(s_map[win_w], sL, gr, Minv, gm);
+      mapped(Minv, s_s[s_piv[win_jj]].x, xj);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = xj[k] - s_r[pref].x[k];
+      partner = nearest(s_s, n, s_r[tid], Minv, t, gm, &best, D);
+    }
+    if (tid < n) p.perm[(long)n0 + tid] = partner;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const float rms = matched ? __uint_as_float((unsigned)(best_key >> 32)) : 0.f;
+  const bool frames = !(flags & CHM_MATCH_NO_LATTICE);
+  oi[0] = make_int4(__float_as_int(rms), __float_as_int(matched ? s_f[F_MAXD] : 0.f), __float_as_int(frames ? scale : 0.f),
+                    __float_as_int(frames ? ell : 0.f));
+  oi[1] = make_int4(matched ? s_map[win_w] : -1, matched ? s_piv[win_jj] : -1, n_maps, total);
+  oi[2] = make_int4(s_i[I_NSURV], matched ? 1 : 0, flags, r);
+  oi[3] = make_int4(0, 0, 0, 0);
+}
+
+}  // namespace
+
+struct chm_match {
+  int B = 0, R = 0;
+  long N = 0, NR = 0;
+  int* d_ints = nullptr;  // one allocation: off [B + 1], roff [R + 1], ref_of [B]
+  const int* d_off = nullptr;
+  const int* d_roff = nullptr;
+  const int* d_ref_of = nullptr;
+};
+
+namespace {
+int offsets(const int32_t* nat, int count, const char* what, std::vector<int>& offs, long* total) {
+  offs.assign((size_t)count + 1, 0);
+  long N = 0;
+  for (int g = 0; g < count; ++g) {
+    if (nat[g] <= 0) return fail(CHM_E_ARG, std::string(what) + "[" + std::to_string(g) + "] must be >= 1");
+    if (nat[g] > kMaxAtoms)
+      return fail(CHM_E_UNSUPPORTED, std::string(what) + "[" + std::to_string(g) + "] = " + std::to_string(nat[g]) +
+                                         ": the matcher holds at most " + std::to_string(kMaxAtoms) + " atoms per crystal");
+    N += nat[g];
+    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one match plan");
+    offs[(size_t)g + 1] = (int)N;
+  }
+  *total = N;
+  return CHM_OK;
+}
+}  // namespace
+
+extern "C" int chm_match_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms, int num_refs,
+                                const int32_t* h_ref_of, chm_match** out) {
+  static_assert(sizeof(chm_match_record) == 64, "the record is 64 bytes");
+  if (!out) return fail(CHM_E_ARG, "out is NULL");
+  *out = nullptr;
+  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
+  if (!h_ref_natoms) return fail(CHM_E_ARG, "ref_natoms is NULL");
+  if (!h_ref_of) return fail(CHM_E_ARG, "ref_of is NULL");
+  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
+  if (num_refs <= 0) return fail(CHM_E_ARG, "num_refs must be >= 1");
+  std::vector<int> offs, roffs;
+  long N = 0, NR = 0;
+  int rc;
+  if ((rc = offsets(h_natoms, num_graphs, "natoms", offs, &N))) return rc;
+  if ((rc = offsets(h_ref_natoms, num_refs, "ref_natoms", roffs, &NR))) return rc;
+  for (int g = 0; g < num_graphs; ++g)
+    if (h_ref_of[g] < -1 || h_ref_of[g] >= num_refs)
+      return fail(CHM_E_ARG, "ref_of[" + std::to_string(g) + "] = " + std::to_string(h_ref_of[g]) + " outside [-1, " +
+                                 std::to_string(num_refs) + ")");
+  std::vector<int> all(offs);
+  all.insert(all.end(), roffs.begin(), roffs.end());
+  all.insert(all.end(), h_ref_of, h_ref_of + num_graphs);
+  chm_match* p = new chm_match;
+  p->B = num_graphs, p->R = num_refs, p->N = N, p->NR = NR;
+  hipError_t e;
+  if ((e = hipMalloc((void**)&p->d_ints, all.size() * sizeof(int))) == hipSuccess)
+    e = hipMemcpy(p->d_ints, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (p->d_ints) (void)hipFree(p->d_ints);
+    delete p;
+    return fail(CHM_E_HIP, std::string("chm_match_create: ") + hipGetErrorString(e));
+  }
+  p->d_off = p->d_ints;
+  p->d_roff = p->d_off + offs.size();
+  p->d_ref_of = p->d_roff + roffs.size();
+  *out = p;
+  return CHM_OK;
+}
+
+extern "C" void chm_match_destroy(chm_match* p) {
+  if (!p) return;
+  (void)hipFree(p->d_ints);
+  delete p;
+}
+
+namespace {
+int want(const void* ptr, long n, long expect, const char* name, const char* unit) {
+  if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
+  if (n != expect)
+    return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the match plan needs " +
+                               std::to_string(expect));
+  return CHM_OK;
+}
+}  // namespace
+
+extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, size_t n_record_bytes,
+                             const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                             const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                             size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                             const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                             int64_t n_ref_lattices, float ltol, float stol, float angle_tol, void* d_out,
+                             size_t n_out_bytes, int32_t* d_perm, int64_t n_perm, void* stream) {
+  if (!p) return fail(CHM_E_ARG, "match plan is NULL");
+  int rc;
+  if ((rc = want(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if (reinterpret_cast<uintptr_t>(d_cell_records) % 16) return fail(CHM_E_ARG, "cell records must be 16-byte aligned");
+  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
+  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
+  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
+  if ((rc = want(d_ref_cell_records, (long)n_ref_record_bytes, 128L * p->R, "ref cell records", "bytes"))) return rc;
+  if (reinterpret_cast<uintptr_t>(d_ref_cell_records) % 16)
+    return fail(CHM_E_ARG, "ref cell records must be 16-byte aligned");
+  if ((rc = want(d_ref_atom_types, n_ref_atom_types, p->NR, "ref_atom_types [NR]", "elements"))) return rc;
+  if ((rc = want(d_ref_frac, n_ref_frac, 3 * p->NR, "ref_frac [NR,3]", "elements"))) return rc;
+  if ((rc = want(d_ref_lattices, n_ref_lattices, 9L * p->R, "ref_lattices [R,3,3]", "elements"))) return rc;
+  if (!(ltol > 0.f && ltol <= CHM_MATCH_MAX_LTOL)) return fail(CHM_E_ARG, "ltol must be in (0, 1]");
+  if (!(stol > 0.f && stol <= CHM_MATCH_MAX_STOL)) return fail(CHM_E_ARG, "stol must be in (0, 1]");
+  if (!(angle_tol > 0.f && angle_tol <= CHM_MATCH_MAX_ANGLE_TOL))
+    return fail(CHM_E_ARG, "angle_tol must be in (0, 30] degrees");
+  if ((rc = want(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
+  if (!d_perm && n_perm != 0) return fail(CHM_E_ARG, "perm is NULL but " + std::to_string(n_perm) + " elements");
+  if (d_perm && (rc = want(d_perm, n_perm, p->N, "perm [N]", "elements"))) return rc;
+  MatchArgs a;
+  a.rec = static_cast<const chm_cell_record*>(d_cell_records);
+  a.types = reinterpret_cast<const long long*>(d_atom_types);
+  a.x = d_frac;
+  a.lat = d_lattices;
+  a.off = p->d_off;
+  a.rrec = static_cast<const chm_cell_record*>(d_ref_cell_records);
+  a.rtypes = reinterpret_cast<const long long*>(d_ref_atom_types);
+  a.rx = d_ref_frac;
+  a.rlat = d_ref_lattices;
+  a.roff = p->d_roff;
+  a.ref_of = p->d_ref_of;
+  a.ltol = ltol;
+  a.stol = stol;
+  a.angle_tol = angle_tol;
+  a.out = static_cast<int4*>(d_out);
+  a.perm = d_perm;
+  hipLaunchKernelGGL(k_match, dim3(p->B), dim3(kBlock), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return CHM_OK;
+}

@@ -605,6 +605,108 @@ std::tuple<at::Tensor, at::Tensor> symmetry(const at::Tensor& atom_types, const 
   return {rec, ops};
 }
 
+// Matching against references (chm_cell_run on both lists + chm_match_run on one stream): (records uint8 [B,64] =
+// the chm_match_record of every crystal; perm int32 [N], or [0] unless `perm`). ref_of: one reference index per
+// crystal, -1 for none. Plans are cached per (natoms, ref_natoms, ref_of, device), the last 8.
+struct MatchPlans {
+  struct Entry {
+    std::vector<int64_t> natoms, ref_natoms, ref_of;
+    int device;
+    chm_cell *cells, *ref_cells;
+    chm_match* match;
+  };
+  std::mutex mu;
+  std::vector<Entry> plans;
+  static void drop(Entry& e) {
+    chm_cell_destroy(e.cells);
+    chm_cell_destroy(e.ref_cells);
+    chm_match_destroy(e.match);
+  }
+  Entry get(const std::vector<int64_t>& natoms, const std::vector<int64_t>& ref_natoms,
+            const std::vector<int64_t>& ref_of, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (e.device == device && e.natoms == natoms && e.ref_natoms == ref_natoms && e.ref_of == ref_of) return e;
+    std::vector<int32_t> nat, rnat, of;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    for (int64_t n : ref_natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match: atoms per reference must be >= 1, got ", n);
+      rnat.push_back((int32_t)n);
+    }
+    for (int64_t r : ref_of) {
+      TORCH_CHECK(r >= -1 && r < (int64_t)ref_natoms.size(), "match: ref_of entry ", r, " outside [-1, ",
+                  ref_natoms.size(), ")");
+      of.push_back((int32_t)r);
+    }
+    Entry e{natoms, ref_natoms, ref_of, device, nullptr, nullptr, nullptr};
+    int rc = chm_match_create(nat.data(), (int)nat.size(), rnat.data(), (int)rnat.size(), of.data(), &e.match);
+    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &e.cells);
+    if (rc == CHM_OK) rc = chm_cell_create(rnat.data(), (int)rnat.size(), &e.ref_cells);
+    if (rc != CHM_OK) {
+      drop(e);
+      check(rc, "chm_match_create");
+    }
+    if (plans.size() >= 8) {
+      drop(plans.front());
+      plans.erase(plans.begin());
+    }
+    plans.push_back(e);
+    return e;
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor> match(const at::Tensor& atom_types, const at::Tensor& frac,
+                                         const at::Tensor& lattices, std::vector<int64_t> natoms,
+                                         const at::Tensor& ref_atom_types, const at::Tensor& ref_frac,
+                                         const at::Tensor& ref_lattices, std::vector<int64_t> ref_natoms,
+                                         std::vector<int64_t> ref_of, double ltol, double stol, double angle_tol,
+                                         bool perm) {
+  static MatchPlans* cache = new MatchPlans;
+  TORCH_CHECK(!natoms.empty(), "match: natoms is empty");
+  TORCH_CHECK(!ref_natoms.empty(), "match: ref_natoms is empty");
+  const c10::Device dev = frac.device();
+  need_on(atom_types, dev, at::kLong, "atom_types");
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  need_on(ref_atom_types, dev, at::kLong, "ref_atom_types");
+  need_on(ref_frac, dev, at::kFloat, "ref_frac");
+  need_on(ref_lattices, dev, at::kFloat, "ref_lattices");
+  int64_t N = 0, NR = 0;
+  for (int64_t n : natoms) N += n;
+  for (int64_t n : ref_natoms) NR += n;
+  const int64_t B = (int64_t)natoms.size(), R = (int64_t)ref_natoms.size();
+  TORCH_CHECK((int64_t)ref_of.size() == B, "ref_of: expected ", B, " entries, got ", ref_of.size());
+  need_shape(atom_types, {N}, "atom_types");
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  need_shape(ref_atom_types, {NR}, "ref_atom_types");
+  need_shape(ref_frac, {NR, 3}, "ref_frac");
+  need_shape(ref_lattices, {R, 3, 3}, "ref_lattices");
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  auto plan = cache->get(natoms, ref_natoms, ref_of, dev.index());
+  const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+  at::Tensor cells = at::empty({B, 128}, bytes), ref_cells = at::empty({R, 128}, bytes), rec = at::empty({B, 64}, bytes);
+  at::Tensor pm = at::empty({perm ? N : 0}, at::TensorOptions().dtype(at::kInt).device(dev));
+  check(chm_cell_run(plan.cells, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, 0.1f, 10.0f, cells.data_ptr(),
+                     (size_t)cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_cell_run(plan.ref_cells, ref_lattices.data_ptr<float>(), ref_lattices.numel(), nullptr, 0, 0.1f, 10.0f,
+                     ref_cells.data_ptr(), (size_t)ref_cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_match_run(plan.match, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+                      atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
+                      lattices.numel(), ref_cells.data_ptr(), (size_t)ref_cells.numel(),
+                      ref_atom_types.data_ptr<int64_t>(), ref_atom_types.numel(), ref_frac.data_ptr<float>(),
+                      ref_frac.numel(), ref_lattices.data_ptr<float>(), ref_lattices.numel(), (float)ltol, (float)stol,
+                      (float)angle_tol, rec.data_ptr(), (size_t)rec.numel(), perm ? pm.data_ptr<int32_t>() : nullptr,
+                      pm.numel(), stream()),
+        "chm_match_run");
+  return {rec, pm};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -637,6 +739,9 @@ TORCH_LIBRARY(chemeleon, m) {
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("symmetry(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? require, float symprec, "
         "float angle_tolerance, bool operations) -> (Tensor, Tensor)");
+  m.def("match(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor ref_atom_types, Tensor ref_frac, "
+        "Tensor ref_lattices, int[] ref_natoms, int[] ref_of, float ltol, float stol, float angle_tol, bool perm) -> "
+        "(Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -648,4 +753,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("dedup", dedup);
   m.impl("cell", cell);
   m.impl("symmetry", symmetry);
+  m.impl("match", match);
 }

@@ -1,6 +1,6 @@
 """The tail of Chemeleon.sample(): the optional legs that run on the finished state on the device (the screen,
-chemeleon_amd.screening; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the grouping,
-chemeleon_amd.dedup), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
+chemeleon_amd.screening; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the matching,
+chemeleon_amd.match; the grouping, chemeleon_amd.dedup), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
 
 from typing import Sequence
 
@@ -8,13 +8,13 @@ import numpy as np
 
 
 def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen=None, cell=None, symmetry=None,
-                 dedup=None):
-    """(structures, reports): the tail of sample() with any of its four optional legs, in this order: the screen,
-    the cell, the symmetry, then the grouping, from which the failures of the first three (a screen flag; a
-    required lattice system or crystal system not met) are excluded. Only the structures that pass (with dedup:
+                 dedup=None, match=None):
+    """(structures, reports): the tail of sample() with any of its five optional legs, in this order: the screen,
+    the cell, the symmetry, the matching, then the grouping, from which the failures of the first four (a screen
+    flag; a required lattice system or crystal system not met; with match.require, no match) are excluded. Only the structures that pass (with dedup:
     one representative per group) are copied and converted (in their reduced cells with cell.reduce), each with
-    atoms.info["screen"] / ["cell"] / ["symmetry"] / ["dedup"] for the legs that ran. `reports` is a dict with the
-    report of each leg that ran under the same four names."""
+    atoms.info["screen"] / ["cell"] / ["symmetry"] / ["match"] / ["dedup"] for the legs that ran. `reports` is a
+    dict with the report of each leg that ran under the same five names."""
     from chemeleon_amd.screening import screen_states, selected_atoms
     nat = [int(n) for n in natoms]
     reports = {}
@@ -33,6 +33,11 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
         from chemeleon_amd.symmetry import symmetry_states
         reports["symmetry"] = symmetry_states(nat, atom_types, frac_coords, lattices, symmetry)
         failed = reports["symmetry"].mismatch.copy() if failed is None else failed | reports["symmetry"].mismatch
+    if match is not None:
+        from chemeleon_amd.match import match_states
+        reports["match"] = match_states(nat, atom_types, frac_coords, lattices, match)
+        if match.require:
+            failed = reports["match"].mismatch.copy() if failed is None else failed | reports["match"].mismatch
     if dedup is not None:
         from chemeleon_amd.dedup import dedup_states
         reports["dedup"] = dedup_states(nat, atom_types, frac_coords, lattices, dedup, failed)
@@ -51,6 +56,8 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
             at.info["cell"] = dict(reports["cell"].record(g), index=g, reduced=cell.reduce)
         if "symmetry" in reports:
             at.info["symmetry"] = dict(reports["symmetry"].record(g), index=g)
+        if "match" in reports:
+            at.info["match"] = dict(reports["match"].record(g), index=g)
         if "dedup" in reports:
             at.info["dedup"] = reports["dedup"].record(g)
     return atoms, reports

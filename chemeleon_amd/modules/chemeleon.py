@@ -60,6 +60,7 @@ class Chemeleon(nn.Module):
     last_dedup = None   # the DedupReport of the last sample(..., dedup=...) call
     last_cell = None    # the CellReport of the last sample(..., cell=...) call
     last_symmetry = None  # the SymmetryReport of the last sample(..., symmetry=...) call
+    last_match = None  # the MatchReport of the last sample(..., match=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
@@ -651,7 +652,7 @@ class Chemeleon(nn.Module):
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
                group=None, overlap: bool = True, screen=None, dedup=None, cell=None, symmetry=None,
-               **kw):
+               match=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -700,8 +701,26 @@ class Chemeleon(nn.Module):
         structure gets atoms.info["symmetry"] and the whole report is kept as self.last_symmetry. With require=
         only the structures of that crystal system are returned, and the others take no part in the grouping.
         Like the screen it is for finished structures (ValueError with stream / return_trajectory) and runs on
-        the gathered final state on every rank. Without the keyword nothing of it runs."""
+        the gathered final state on every rank. Without the keyword nothing of it runs.
+
+        match=Match(...) (chemeleon_amd.match): every finished structure is matched against its reference
+        structure on the device (lattice mappings, atom pairing, rms displacement), after the symmetry and before
+        the grouping; each returned structure gets atoms.info["match"] and the whole report is kept as
+        self.last_match (match_rate, rms_mean). With require=True only the structures that match are returned,
+        and the others take no part in the grouping. Like the screen it is for finished structures (ValueError
+        with stream / return_trajectory) and runs on the gathered final state on every rank, with no collective
+        of its own. Without the keyword nothing of it runs."""
         natoms = [n_atoms] * n_samples
+        if match is not None:
+            from chemeleon_amd.match import MAX_ATOMS as MATCH_MAX_ATOMS
+            from chemeleon_amd.match import Match
+            if not isinstance(match, Match):
+                raise ValueError("match must be a chemeleon_amd.Match")
+            if stream or return_trajectory:
+                raise ValueError("match= applies to finished structures: not with stream / return_trajectory")
+            match.ref_of_for(n_samples)  # (a ref_of of the wrong length fails before sampling)
+            if n_atoms > MATCH_MAX_ATOMS:
+                raise ValueError(f"match= holds at most {MATCH_MAX_ATOMS} atoms per crystal, got n_atoms={n_atoms}")
         if symmetry is not None:
             from chemeleon_amd.symmetry import MAX_ATOMS, Symmetry
             if not isinstance(symmetry, Symmetry):
@@ -747,9 +766,10 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
-        if screen is not None or cell is not None or symmetry is not None or dedup is not None:
+        if screen is not None or cell is not None or symmetry is not None or dedup is not None or match is not None:
             from chemeleon_amd.finish import finish_atoms
-            atoms, reports = finish_atoms(natoms, a, x, lat, screen=screen, cell=cell, symmetry=symmetry, dedup=dedup)
+            atoms, reports = finish_atoms(natoms, a, x, lat, screen=screen, cell=cell, symmetry=symmetry, dedup=dedup,
+                                          match=match)
             for leg, report in reports.items():  # (only the legs that were asked for: the others keep their last)
                 setattr(self, "last_" + leg, report)
             return atoms

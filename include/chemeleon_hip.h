@@ -990,6 +990,113 @@ int chm_symm_run(const chm_symm* plan, const void* d_cell_records, size_t n_reco
                  float angle_tolerance, void* d_out, size_t n_out_bytes, void* d_ops, size_t n_ops_bytes,
                  void* stream);
 
+/* Matching finished structures against reference structures on the device: what test_structure_matching of the
+ * reference's scripts/evaluate.py asks of pymatgen on the host (StructureMatcher().fit(ref_st, st), reported as
+ * match rate and RMSD). This is NOT a port of pymatgen: the definition below is this library's own, and how far
+ * the two agree has not been measured. The parameters take StructureMatcher's defaults: ltol = 0.2 (relative
+ * length), stol = 0.3 (fraction of l, below), angle_tol = 5 degrees; scaling is always on.
+ *
+ * Input. A state of B crystals (atom_types int64 [N], compared as their low 32 bits; frac fp32 [N,3]; lattices
+ * fp32 [B,3,3], row vectors), R reference structures packed the same way, ref_of[B] (given at create: crystal g
+ * is matched against reference ref_of[g] in [0, R); -1 = no reference: flag CHM_MATCH_NO_REFERENCE, ref -1,
+ * everything else 0), and the chm_cell_records of the samples and of the references from chm_cell_run on the
+ * same lattices (any tolerances: only T and the flags are read).
+ *
+ * Preconditions, each a flag, no search, matched = 0. CHM_MATCH_NO_LATTICE: one of the two cell records has
+ * CHM_CELL_NOT_REDUCED, CHM_CELL_DEGENERATE or CHM_CELL_NONFINITE, or a reduced volume (below) is not a finite
+ * number > 0. CHM_MATCH_SIZE: n != n_ref. CHM_MATCH_COMPOSITION (tested when the sizes are equal): some type's
+ * atom count differs, compared as integers. Atom counts must be equal: there is no reduction to a primitive
+ * cell, so a supercell sample does not match its primitive reference (a deliberate difference from pymatgen).
+ *
+ * Reduced frames. Ls = T_s L and x' = frac(x adj(T_s)) for the sample, Lr and xr likewise for the reference,
+ * exactly as chm_cell_apply produces them (the same device code). V_s, V_r = |det| of those fp32 cells in fp64,
+ * ((l00 (l11 l22 - l12 l21) - l01 (l10 l22 - l12 l20)) + l02 (l10 l21 - l11 l20)). Scale s = cbrt(V_r / V_s) and
+ * l = cbrt(V_r / n), both in fp64 on one lane and rounded to fp32 once. Pairing cutoff c = stol l (A), fp32. The
+ * scaled sample cell is sLs = s Ls, entry by entry.
+ *
+ * Lattice mappings. Every integer M with entries in {-1, 0, 1} and |det M| = 1, both signs, so that an
+ * enantiomorph matches; index = sum_q (M[q] + 1) 3^q as in the cell search. With L' = M sLs (entries (m0 l0 + m1
+ * l1) + m2 l2) M is accepted when every row length l'_i has |l'_i / lr_i - 1| <= ltol and every inter-row angle
+ * differs from Lr's by at most angle_tol degrees (lengths, angles as in the cell search: accurate sqrtf / acosf).
+ * The accepted M are taken in ascending index; n_mappings counts all of them, the first CHM_MATCH_MAX_MAPPINGS
+ * (256) are used and more than that sets CHM_MATCH_MANY_MAPPINGS.
+ *
+ * Under a mapping. x'' = frac(x' Minv), Minv = det(M) adj(M) in integers, component k = (x0 Minv[0][k] + x1
+ * Minv[1][k]) + x2 Minv[2][k], minus its floorf, 0 where that rounds to 1. The metric is G = 0.5 (G(L') + G(Lr)),
+ * G(A)[i][j] = row_i . row_j: the mean of the two metric tensors, so no rotation has to be found. The length
+ * squared of a fractional vector d is |d|^2 = (u0 d0 + u1 d1) + u2 d2 with u_k = (d0 G[0][k] + d1 G[1][k]) + d2 G[2][k].
+ *
+ * Anchors. p = the first reference atom of the species with the fewest atoms (ties: the smallest type). For
+ * every sample atom j of that species, in node order: t_j = x''_j - xr_p and y_i = x''_i - t_j.
+ *
+ * Pairing of a candidate (M, j). Each reference atom k, in index order, takes the sample atom i of its own type
+ * with the smallest |D|^2, D = (y_i - xr_k) - rintf(y_i - xr_k) per component (one image per component; ties go
+ * to the smallest i). The candidate is given up at the first k whose partner has |D|^2 > c^2 (or not <=) or was
+ * taken by an earlier k. A candidate that pairs every k survives: the pairing is a type-preserving bijection.
+ * This is a nearest-partner rule, not pymatgen's optimal assignment.
+ *
+ * Score of a survivor. m = (sum_k D_k) / n (sums in index order), e_k = D_k - m, rms = sqrtf((sum_k |e_k|^2) /
+ * n) / l, max_dist = sqrtf(max_k |e_k|^2) (A). The candidate counts if rms <= stol. matched = 1 if any candidate
+ * counts; the winner has the smallest rms, ties to the smallest mapping index, then the smallest j: an integer
+ * minimum over (rms bits, position in the mapping list, position in the anchor list), so the record does not
+ * depend on any order.
+ *
+ * Thin cells. With the plane spacings of Lr as in chm_symm_*: a crystal where not 2 c < the smallest spacing
+ * gets CHM_MATCH_THIN and no search: one image per component would not be exact. Below that bound it is: any
+ * image within c has every fractional component under 1/2.
+ *
+ * All per-candidate arithmetic is fp32, every product and sum rounded on its own. The bytes are the same on
+ * every run and for a crystal alone or inside any batch.
+ *
+ * Record: rms, max_dist, scale, l (0 where not computed), mapping (candidate index of the winner, -1), anchor
+ * (the sample atom j of the winner within its crystal, -1), n_mappings, n_candidates (mappings used x anchors),
+ * n_survivors, matched, flags, ref, 16 bytes of 0. Optional second output d_perm int32 [N] (NULL with n_perm =
+ * 0): at node offset of crystal g, for each reference atom k the sample atom (within the crystal) it is paired
+ * with under the winner; -1 everywhere in a crystal that is not matched.
+ *
+ * The plan holds the node offsets of both lists and ref_of on the current device; a crystal or reference of more
+ * than 256 atoms is refused at create with CHM_E_UNSUPPORTED, a ref_of outside [-1, R) with CHM_E_ARG. The run
+ * takes every buffer with its count (cell records 128 bytes, out 64 bytes per crystal, 16-byte aligned); a NULL
+ * pointer, a mismatched count, ltol or stol outside (0, 1] or angle_tol outside (0, 30] return CHM_E_ARG naming
+ * the argument before the first HIP call and nothing is enqueued. It allocates nothing and does not
+ * synchronise: legal under stream capture. */
+#define CHM_MATCH_NO_REFERENCE 1   /* ref_of = -1 */
+#define CHM_MATCH_NO_LATTICE 2     /* a cell record without a reduced cell, or a volume not > 0 */
+#define CHM_MATCH_SIZE 4           /* n != n_ref */
+#define CHM_MATCH_COMPOSITION 8    /* element counts differ */
+#define CHM_MATCH_THIN 16          /* 2 stol l is not below the smallest plane spacing of Lr */
+#define CHM_MATCH_MANY_MAPPINGS 32 /* more than CHM_MATCH_MAX_MAPPINGS accepted: the first ones were used */
+#define CHM_MATCH_MAX_MAPPINGS 256
+#define CHM_MATCH_MAX_LTOL 1.0f
+#define CHM_MATCH_MAX_STOL 1.0f
+#define CHM_MATCH_MAX_ANGLE_TOL 30.0f
+typedef struct {
+  float rms;                  /* of the winner, in units of l */
+  float max_dist;             /* of the winner (A) */
+  float scale;                /* s */
+  float l;                    /* cbrt(V_r / n) (A) */
+  int32_t mapping;            /* candidate index of the winner's M, or -1 */
+  int32_t anchor;             /* the winner's sample atom j within the crystal, or -1 */
+  int32_t n_mappings;         /* accepted M (all of them) */
+  int32_t n_candidates;       /* (M, j) tried */
+  int32_t n_survivors;        /* candidates that paired every atom */
+  int32_t matched;            /* 1 or 0 */
+  int32_t flags;              /* CHM_MATCH_* bits */
+  int32_t ref;                /* ref_of of the crystal */
+  int32_t reserved[4];        /* written as 0 */
+} chm_match_record;           /* 64 bytes */
+typedef struct chm_match chm_match;
+int chm_match_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms, int num_refs,
+                     const int32_t* h_ref_of, chm_match** out);
+void chm_match_destroy(chm_match* plan);
+int chm_match_run(const chm_match* plan, const void* d_cell_records, size_t n_record_bytes,
+                  const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                  const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                  size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                  const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices, int64_t n_ref_lattices,
+                  float ltol, float stol, float angle_tol, void* d_out, size_t n_out_bytes, int32_t* d_perm,
+                  int64_t n_perm, void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
