@@ -316,5 +316,10 @@ struct ConstrainArgs {
 // what: bit 0 types, bit 1 lattices, bit 2 coordinates (fields without a mask are skipped)
 hipError_t constrain(const ConstrainArgs& g, int what, hipStream_t s);
 
+// (dedup.hip) the leader scan k_dedup_lead over a bit matrix [B, W] (bit h of row g = (g < h and they match)):
+// group / count [B], reps [B] workspace; a crystal with flags[g] != 0 or exclude[g] != 0 (either may be null) gets -1
+hipError_t dedup_lead(int B, int W, const unsigned* match, const int* flags, const unsigned char* exclude, int* reps,
+                      int* group, int* count, hipStream_t s);
+
 }  // namespace chm
 

@@ -342,6 +342,22 @@ bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
 
 }  // namespace
 
+// k_dedup_lead for the units that fill a bit matrix of their own (match.hip's grouping by matching)
+hipError_t chm::dedup_lead(int B, int W, const unsigned* match, const int* flags, const unsigned char* exclude, int* reps,
+                           int* group, int* count, hipStream_t s) {
+  LeadArgs l;
+  l.B = B;
+  l.W = W;
+  l.match = match;
+  l.flags = flags;
+  l.exclude = exclude;
+  l.reps = reps;
+  l.group = group;
+  l.count = count;
+  hipLaunchKernelGGL(k_dedup_lead, dim3(1), dim3(kLeadBlock), 0, s, l);
+  return hipGetLastError();
+}
+
 struct chm_dedup {
   int B = 0;
   long N = 0;

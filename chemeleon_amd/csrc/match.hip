@@ -12,10 +12,16 @@
 // order pass by pass) are staged in LDS. The candidates (M, t_j) are spread over the block, one thread each, with a
 // 256-bit "taken" set per thread in LDS. The winner is a 64-bit integer minimum in LDS over (rms bits, mapping
 // position, anchor position), every count an integer add, so the record does not depend on any order.
+//
+// Grouping a batch by pairwise matching (chm_match_group_*): the same block body (match_block) runs once per pair
+// (h, g), h < g, of crystals of one state with equal atom counts (k_match_pairs), crystal h as the reference side;
+// a match sets bit g of row h of a bit matrix with one atomicOr, k_dedup_lead (dedup.hip) applies the leader rule
+// to the matrix and k_match_group_gather writes each crystal's record against its leader.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 #include <math.h>
+#include <string.h>
 
 #include <cstdint>
 #include <string>
@@ -164,8 +170,12 @@ enum { I_COMP = 0, I_MINCNT, I_PTYPE, I_PREF, I_VOLOK, I_NSURV, I_COUNT };
 // LDS floats of the block
 enum { F_SCALE = 0, F_ELL, F_MAXD, F_COUNT };
 
-// Block g (four waves) = crystal g.
-__global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
+// One block (four waves) = sample crystal g against reference r. kPairs = false is k_match (the record of 64
+// bytes at oi, the pairing in p.perm); kPairs = true is k_match_pairs, where both sides come from one state: the
+// compact record {rms, max_dist, flags, matched} at oi[0] and, on a match, `bit` or-ed into *bit_word.
+template <bool kPairs>
+__device__ __forceinline__ void match_block(const MatchArgs& p, const int g, const int r, int4* oi, unsigned* bit_word,
+                                            unsigned bit) {
   __shared__ Atom s_s[kMaxAtoms];  // the sample
   __shared__ Atom s_r[kMaxAtoms];  // its reference
   __shared__ int s_map[kMaxMaps];  // accepted candidate indices, ascending
@@ -174,20 +184,20 @@ __global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
   __shared__ float s_Ls[9], s_Lr[9], s_f[F_COUNT];
   __shared__ int s_i[I_COUNT], s_wcnt[kBlock / 64];
   __shared__ unsigned long long s_best;
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = p.off[g], n = p.off[g + 1] - n0;  // (1 <= n <= kMaxAtoms: chm_match_create)
-  const int r = p.ref_of[g];                       // (-1 <= r < R: chm_match_create)
-  int4* oi = p.out + 4 * (long)g;
   // (r, n, nr and everything read from the cell records are the same in every thread: the branches on them are uniform)
-  if (r < 0) {
-    if (p.perm && tid < n) p.perm[(long)n0 + tid] = -1;
-    if (tid == 0) {
-      oi[0] = make_int4(0, 0, 0, 0);
-      oi[1] = make_int4(-1, -1, 0, 0);
-      oi[2] = make_int4(0, 0, CHM_MATCH_NO_REFERENCE, -1);
-      oi[3] = make_int4(0, 0, 0, 0);
+  if constexpr (!kPairs) {
+    if (r < 0) {
+      if (p.perm && tid < n) p.perm[(long)n0 + tid] = -1;
+      if (tid == 0) {
+        oi[0] = make_int4(0, 0, 0, 0);
+        oi[1] = make_int4(-1, -1, 0, 0);
+        oi[2] = make_int4(0, 0, CHM_MATCH_NO_REFERENCE, -1);
+        oi[3] = make_int4(0, 0, 0, 0);
+      }
+      return;
     }
-    return;
   }
   const int m0 = p.roff[r], nr = p.roff[r + 1] - m0;
   const chm_cell_record* rec = p.rec + g;
@@ -372,7 +382,7 @@ __global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
   const int win_w = (int)((best_key >> 8) & 0xffu), win_jj = (int)(best_key & 0xffu);
 
   // ---- the winner's pairing, recomputed: reference atom k -> its sample atom
-  if (p.perm) {
+  if (!kPairs && p.perm) {
     int partner = -1;
     if (matched && tid < n) {
       float Minv[9], gm[6], t[3], xj[3], best, D[3];
@@ -387,12 +397,87 @@ __global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
   __syncthreads();
   if (tid != 0) return;
   const float rms = matched ? __uint_as_float((unsigned)(best_key >> 32)) : 0.f;
+  if constexpr (kPairs) {
+    oi[0] = make_int4(__float_as_int(rms), __float_as_int(matched ? s_f[F_MAXD] : 0.f), flags, matched ? 1 : 0);
+    if (matched) atomicOr(bit_word, bit);
+    return;
+  }
   const bool frames = !(flags & CHM_MATCH_NO_LATTICE);
   oi[0] = make_int4(__float_as_int(rms), __float_as_int(matched ? s_f[F_MAXD] : 0.f), __float_as_int(frames ? scale : 0.f),
                     __float_as_int(frames ? ell : 0.f));
   oi[1] = make_int4(matched ? s_map[win_w] : -1, matched ? s_piv[win_jj] : -1, n_maps, total);
   oi[2] = make_int4(s_i[I_NSURV], matched ? 1 : 0, flags, r);
   oi[3] = make_int4(0, 0, 0, 0);
+}
+
+// Block g = crystal g against reference ref_of[g] (-1 <= ref_of[g] < R: chm_match_create).
+__global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
+  const int g = blockIdx.x;
+  match_block<false>(p, g, p.ref_of[g], p.out + 4 * (long)g, nullptr, 0u);
+}
+
+struct PairArgs {
+  MatchArgs m;                   // the reference side aliases the sample side; ref_of, out and perm are unused
+  const int2* pairs;             // [P] (h, g), h < g, n_h == n_g
+  const unsigned char* exclude;  // NULL: none excluded
+  unsigned* bits;                // [B, W]: bit g of row h = (h < g and they match), cleared by k_match_group_cells
+  int W;
+  int4* pout;                    // [P] {rms, max_dist, flags, matched}
+};
+
+// Block b = pair (h, g) = pairs[b]: crystal g as the sample against crystal h as the reference, both of one state.
+__global__ __launch_bounds__(kBlock) void k_match_pairs(PairArgs q) {
+  const int2 pr = q.pairs[blockIdx.x];
+  const int h = pr.x, g = pr.y;  // (0 <= h < g < B: chm_match_group_create)
+  int4* oi = q.pout + blockIdx.x;
+  // (uniform over the block: nothing is staged for a pair that cannot be searched)
+  int early = 0;
+  if (q.exclude && (q.exclude[h] || q.exclude[g])) early |= CHM_MATCH_EXCLUDED;
+  if ((q.m.rec[h].flags | q.m.rec[g].flags) & kNoCell) early |= CHM_MATCH_NO_LATTICE;
+  if (early) {
+    if (threadIdx.x == 0) oi[0] = make_int4(0, 0, early, 0);
+    return;
+  }
+  match_block<true>(q.m, g, h, oi, q.bits + (long)h * q.W + (g >> 5), 1u << (g & 31));
+}
+
+struct GroupArgs {
+  int B;
+  const chm_cell_record* rec;
+  const unsigned char* exclude;
+  int* nocell;       // [B] CHM_MATCH_NO_LATTICE or 0: k_dedup_lead's flags
+  unsigned* bits;    // [B, W] the match matrix
+  int W;
+  const int* group;  // [B] of k_dedup_lead
+  const int* first;  // [B] crystal g's first pair
+  const int* rank;   // [B] crystals before g with g's atom count: pair (h, g) is first[g] + rank[h]
+  const int4* pout;
+  int4* out;         // [B] records of 32 bytes
+};
+
+// Thread g: has crystal g a reduced cell? The grid also clears the match matrix in front of k_match_pairs (a
+// kernel, not a memset node: the sequence is replayed from captured graphs).
+__global__ __launch_bounds__(kBlock) void k_match_group_cells(GroupArgs p) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  for (long w = g; w < (long)p.B * p.W; w += (long)gridDim.x * kBlock) p.bits[w] = 0u;
+  if (g < p.B) p.nocell[g] = (p.rec[g].flags & kNoCell) ? CHM_MATCH_NO_LATTICE : 0;
+}
+
+// Thread g: the record of crystal g's pair with its leader.
+__global__ __launch_bounds__(kBlock) void k_match_group_gather(GroupArgs p) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= p.B) return;
+  const int lead = p.group[g];
+  int4 a = make_int4(0, 0, 0, 0), b = make_int4(-1, -1, 0, 0);
+  if (lead < 0) {
+    a.z = p.nocell[g] | ((p.exclude && p.exclude[g]) ? CHM_MATCH_EXCLUDED : 0);
+  } else if (lead != g) {
+    const int at = p.first[g] + p.rank[lead];
+    a = p.pout[at];
+    b.x = lead, b.y = at;
+  }
+  p.out[2 * (long)g] = a;
+  p.out[2 * (long)g + 1] = b;
 }
 
 }  // namespace
@@ -525,6 +610,173 @@ extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, siz
   a.out = static_cast<int4*>(d_out);
   a.perm = d_perm;
   hipLaunchKernelGGL(k_match, dim3(p->B), dim3(kBlock), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return CHM_OK;
+}
+
+// ---- grouping a batch by pairwise matching (chm_match_group_*): k_match_pairs over the plan's pair table into the
+// bit matrix, k_dedup_lead (dedup.hip) over the matrix, k_match_group_gather for the members' records
+struct chm_match_group {
+  int B = 0;
+  long N = 0, P = 0;
+  char* d_mem = nullptr;  // one allocation: off [B + 1], first [B], rank [B], (padding), pairs [P] int2
+  const int* d_off = nullptr;
+  const int* d_first = nullptr;
+  const int* d_rank = nullptr;
+  const int2* d_pairs = nullptr;
+};
+
+namespace {
+size_t align16(size_t v) { return (v + 15) / 16 * 16; }
+size_t group_bits_bytes(int B) { return align16((size_t)B * (size_t)((B + 31) / 32) * sizeof(unsigned)); }
+}  // namespace
+
+extern "C" int chm_match_group_create(const int32_t* h_natoms, int num_graphs, chm_match_group** out) {
+  static_assert(sizeof(chm_match_group_record) == 32 && sizeof(chm_match_pair_record) == 16, "the records' sizes");
+  if (!out) return fail(CHM_E_ARG, "out is NULL");
+  *out = nullptr;
+  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
+  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
+  std::vector<int> offs;
+  long N = 0;
+  int rc;
+  if ((rc = offsets(h_natoms, num_graphs, "natoms", offs, &N))) return rc;
+  const int B = num_graphs;
+  // rank[g] = crystals before g with g's atom count; P = sum of the ranks, counted before anything is built
+  std::vector<int> seen(kMaxAtoms + 1, 0), rank((size_t)B), first((size_t)B);
+  long P = 0;
+  for (int g = 0; g < B; ++g) {
+    rank[g] = seen[h_natoms[g]]++;
+    if (P > INT32_MAX - (long)rank[g])
+      return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 pairs of equal atom count: they do not fit one grid");
+    first[g] = (int)P;
+    P += rank[g];
+  }
+  std::vector<int2> pairs((size_t)P);
+  std::vector<std::vector<int>> by_size(kMaxAtoms + 1);
+  for (int g = 0; g < B; ++g) {
+    std::vector<int>& earlier = by_size[h_natoms[g]];
+    for (size_t k = 0; k < earlier.size(); ++k) pairs[(size_t)first[g] + k] = make_int2(earlier[k], g);
+    earlier.push_back(g);
+  }
+  const size_t n_ints = (size_t)3 * B + 1, ints_bytes = align16(n_ints * sizeof(int));
+  std::vector<char> host(ints_bytes + (size_t)P * sizeof(int2), 0);
+  int* hi = reinterpret_cast<int*>(host.data());
+  for (int g = 0; g <= B; ++g) hi[g] = offs[g];
+  for (int g = 0; g < B; ++g) hi[B + 1 + g] = first[g], hi[2 * B + 1 + g] = rank[g];
+  if (P) memcpy(host.data() + ints_bytes, pairs.data(), (size_t)P * sizeof(int2));
+  chm_match_group* p = new chm_match_group;
+  p->B = B, p->N = N, p->P = P;
+  hipError_t e;
+  if ((e = hipMalloc((void**)&p->d_mem, host.size())) == hipSuccess)
+    e = hipMemcpy(p->d_mem, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (p->d_mem) (void)hipFree(p->d_mem);
+    delete p;
+    return fail(CHM_E_HIP, std::string("chm_match_group_create: ") + hipGetErrorString(e));
+  }
+  p->d_off = reinterpret_cast<const int*>(p->d_mem);
+  p->d_first = p->d_off + B + 1;
+  p->d_rank = p->d_first + B;
+  p->d_pairs = reinterpret_cast<const int2*>(p->d_mem + ints_bytes);
+  *out = p;
+  return CHM_OK;
+}
+
+extern "C" void chm_match_group_destroy(chm_match_group* p) {
+  if (!p) return;
+  (void)hipFree(p->d_mem);
+  delete p;
+}
+
+extern "C" int64_t chm_match_group_num_pairs(const chm_match_group* p) { return p ? p->P : 0; }
+
+// the bit matrix [B, ceil(B/32)] words, the representatives' list [B], the cell flags [B]
+extern "C" size_t chm_match_group_workspace_bytes(const chm_match_group* p) {
+  if (!p) return 0;
+  return group_bits_bytes(p->B) + 2 * (size_t)p->B * sizeof(int);
+}
+
+extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_records, size_t n_record_bytes,
+                                   const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                                   int64_t n_frac, const float* d_lattices, int64_t n_lattices,
+                                   const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol, float angle_tol,
+                                   int32_t* d_group, int64_t n_group, int32_t* d_count, int64_t n_count, void* d_out,
+                                   size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!p) return fail(CHM_E_ARG, "match-group plan is NULL");
+  int rc;
+  if ((rc = want(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if (reinterpret_cast<uintptr_t>(d_cell_records) % 16) return fail(CHM_E_ARG, "cell records must be 16-byte aligned");
+  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
+  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
+  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
+  if (!d_exclude && n_exclude != 0)
+    return fail(CHM_E_ARG, "exclude is NULL but " + std::to_string(n_exclude) + " elements");
+  if (d_exclude && (rc = want(d_exclude, n_exclude, p->B, "exclude [B]", "elements"))) return rc;
+  if (!(ltol > 0.f && ltol <= CHM_MATCH_MAX_LTOL)) return fail(CHM_E_ARG, "ltol must be in (0, 1]");
+  if (!(stol > 0.f && stol <= CHM_MATCH_MAX_STOL)) return fail(CHM_E_ARG, "stol must be in (0, 1]");
+  if (!(angle_tol > 0.f && angle_tol <= CHM_MATCH_MAX_ANGLE_TOL))
+    return fail(CHM_E_ARG, "angle_tol must be in (0, 30] degrees");
+  if ((rc = want(d_group, n_group, p->B, "group [B]", "elements"))) return rc;
+  if ((rc = want(d_count, n_count, p->B, "count [B]", "elements"))) return rc;
+  if ((rc = want(d_out, (long)n_out_bytes, 32L * p->B, "out", "bytes"))) return rc;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
+  if (p->P == 0) {
+    if (n_pair_bytes != 0) return fail(CHM_E_ARG, "pair records: " + std::to_string(n_pair_bytes) + " bytes, the plan has no pair");
+  } else if ((rc = want(d_pair_records, (long)n_pair_bytes, 16L * p->P, "pair records", "bytes"))) {
+    return rc;
+  }
+  if (reinterpret_cast<uintptr_t>(d_pair_records) % 16) return fail(CHM_E_ARG, "pair records must be 16-byte aligned");
+  if (!d_workspace) return fail(CHM_E_ARG, "workspace is NULL");
+  const size_t need = chm_match_group_workspace_bytes(p);
+  if (workspace_bytes < need)
+    return fail(CHM_E_ARG, "workspace: " + std::to_string(workspace_bytes) + " bytes, the match grouping needs " +
+                               std::to_string(need));
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(CHM_E_ARG, "workspace must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = p->B, W = (B + 31) / 32;
+  unsigned* bits = static_cast<unsigned*>(d_workspace);
+  int* reps = reinterpret_cast<int*>(static_cast<char*>(d_workspace) + group_bits_bytes(B));
+  int* nocell = reps + B;
+  GroupArgs ga;
+  ga.B = B;
+  ga.rec = static_cast<const chm_cell_record*>(d_cell_records);
+  ga.exclude = d_exclude;
+  ga.nocell = nocell;
+  ga.bits = bits;
+  ga.W = W;
+  ga.group = d_group;
+  ga.first = p->d_first;
+  ga.rank = p->d_rank;
+  ga.pout = static_cast<const int4*>(d_pair_records);
+  ga.out = static_cast<int4*>(d_out);
+  const dim3 per_crystal((unsigned)((B + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(k_match_group_cells, per_crystal, dim3(kBlock), 0, s, ga);
+  HIPCHK(hipGetLastError());
+  if (p->P) {
+    PairArgs a;
+    a.m.rec = a.m.rrec = ga.rec;
+    a.m.types = a.m.rtypes = reinterpret_cast<const long long*>(d_atom_types);
+    a.m.x = a.m.rx = d_frac;
+    a.m.lat = a.m.rlat = d_lattices;
+    a.m.off = a.m.roff = p->d_off;
+    a.m.ref_of = nullptr;
+    a.m.ltol = ltol;
+    a.m.stol = stol;
+    a.m.angle_tol = angle_tol;
+    a.m.out = nullptr;
+    a.m.perm = nullptr;
+    a.pairs = p->d_pairs;
+    a.exclude = d_exclude;
+    a.bits = bits;
+    a.W = W;
+    a.pout = static_cast<int4*>(d_pair_records);
+    hipLaunchKernelGGL(k_match_pairs, dim3((unsigned)p->P), dim3(kBlock), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(chm::dedup_lead(B, W, bits, nocell, d_exclude, reps, d_group, d_count, s));
+  hipLaunchKernelGGL(k_match_group_gather, per_crystal, dim3(kBlock), 0, s, ga);
   HIPCHK(hipGetLastError());
   return CHM_OK;
 }

@@ -707,6 +707,94 @@ std::tuple<at::Tensor, at::Tensor> match(const at::Tensor& atom_types, const at:
   return {rec, pm};
 }
 
+// Grouping by pairwise matching (chm_cell_run + chm_match_group_run on one stream): (group [B] int32: the
+// representative's index or -1, count [B] int32: the group's size at a representative, records uint8 [B,32] = the
+// chm_match_group_record of every crystal, pair records uint8 [P,16] in the plan's pair order). exclude: a bool /
+// uint8 tensor [B] of crystals that take no part, or None. Plans are cached per (natoms, device), the last 8.
+struct MatchGroupPlans {
+  struct Entry {
+    std::vector<int64_t> natoms;
+    int device;
+    chm_cell* cells;
+    chm_match_group* group;
+  };
+  std::mutex mu;
+  std::vector<Entry> plans;
+  static void drop(Entry& e) {
+    chm_cell_destroy(e.cells);
+    chm_match_group_destroy(e.group);
+  }
+  Entry get(const std::vector<int64_t>& natoms, int device) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : plans)
+      if (e.device == device && e.natoms == natoms) return e;
+    std::vector<int32_t> nat;
+    for (int64_t n : natoms) {
+      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match_group: atoms per crystal must be >= 1, got ", n);
+      nat.push_back((int32_t)n);
+    }
+    Entry e{natoms, device, nullptr, nullptr};
+    int rc = chm_match_group_create(nat.data(), (int)nat.size(), &e.group);
+    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &e.cells);
+    if (rc != CHM_OK) {
+      drop(e);
+      check(rc, "chm_match_group_create");
+    }
+    if (plans.size() >= 8) {
+      drop(plans.front());
+      plans.erase(plans.begin());
+    }
+    plans.push_back(e);
+    return e;
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> match_group(const at::Tensor& atom_types, const at::Tensor& frac,
+                                                                       const at::Tensor& lattices,
+                                                                       std::vector<int64_t> natoms,
+                                                                       const c10::optional<at::Tensor>& exclude,
+                                                                       double ltol, double stol, double angle_tol) {
+  static MatchGroupPlans* cache = new MatchGroupPlans;
+  TORCH_CHECK(!natoms.empty(), "match_group: natoms is empty");
+  const c10::Device dev = frac.device();
+  need_on(atom_types, dev, at::kLong, "atom_types");
+  need_on(frac, dev, at::kFloat, "frac");
+  need_on(lattices, dev, at::kFloat, "lattices");
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  need_shape(atom_types, {N}, "atom_types");
+  need_shape(frac, {N, 3}, "frac");
+  need_shape(lattices, {B, 3, 3}, "lattices");
+  const uint8_t* ex = nullptr;
+  if (exclude.has_value()) {
+    TORCH_CHECK(exclude->scalar_type() == at::kBool || exclude->scalar_type() == at::kByte,
+                "exclude: expected bool or uint8, got ", exclude->scalar_type());
+    need_on(*exclude, dev, exclude->scalar_type(), "exclude");
+    need_shape(*exclude, {B}, "exclude");
+    ex = static_cast<const uint8_t*>(exclude->data_ptr());
+  }
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  auto plan = cache->get(natoms, dev.index());
+  const int64_t P = chm_match_group_num_pairs(plan.group);
+  const size_t ws_bytes = chm_match_group_workspace_bytes(plan.group);
+  const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+  const auto ints = at::TensorOptions().dtype(at::kInt).device(dev);
+  at::Tensor cells = at::empty({B, 128}, bytes), rec = at::empty({B, 32}, bytes), pairs = at::empty({P, 16}, bytes),
+             ws = at::empty({(int64_t)ws_bytes}, bytes), group = at::empty({B}, ints), count = at::empty({B}, ints);
+  check(chm_cell_run(plan.cells, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, 0.1f, 10.0f, cells.data_ptr(),
+                     (size_t)cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_match_group_run(plan.group, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+                            atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
+                            lattices.numel(), ex, ex ? B : 0, (float)ltol, (float)stol, (float)angle_tol,
+                            group.data_ptr<int32_t>(), group.numel(), count.data_ptr<int32_t>(), count.numel(),
+                            rec.data_ptr(), (size_t)rec.numel(), P ? pairs.data_ptr() : nullptr, (size_t)pairs.numel(),
+                            ws.data_ptr(), ws_bytes, stream()),
+        "chm_match_group_run");
+  return {group, count, rec, pairs};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -742,6 +830,8 @@ TORCH_LIBRARY(chemeleon, m) {
   m.def("match(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor ref_atom_types, Tensor ref_frac, "
         "Tensor ref_lattices, int[] ref_natoms, int[] ref_of, float ltol, float stol, float angle_tol, bool perm) -> "
         "(Tensor, Tensor)");
+  m.def("match_group(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? exclude, float ltol, "
+        "float stol, float angle_tol) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -754,4 +844,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("cell", cell);
   m.impl("symmetry", symmetry);
   m.impl("match", match);
+  m.impl("match_group", match_group);
 }

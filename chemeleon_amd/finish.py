@@ -1,6 +1,6 @@
 """The tail of Chemeleon.sample(): the optional legs that run on the finished state on the device (the screen,
 chemeleon_amd.screening; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the matching,
-chemeleon_amd.match; the grouping, chemeleon_amd.dedup), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
+chemeleon_amd.match; the grouping, chemeleon_amd.dedup or, with a MatchDedup, chemeleon_amd.match_group), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
 
 from typing import Sequence
 
@@ -39,8 +39,12 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
         if match.require:
             failed = reports["match"].mismatch.copy() if failed is None else failed | reports["match"].mismatch
     if dedup is not None:
-        from chemeleon_amd.dedup import dedup_states
-        reports["dedup"] = dedup_states(nat, atom_types, frac_coords, lattices, dedup, failed)
+        from chemeleon_amd.match_group import MatchDedup, match_group_states
+        if isinstance(dedup, MatchDedup):  # (grouping by matching instead of by fingerprints)
+            reports["dedup"] = match_group_states(nat, atom_types, frac_coords, lattices, dedup, failed)
+        else:
+            from chemeleon_amd.dedup import dedup_states
+            reports["dedup"] = dedup_states(nat, atom_types, frac_coords, lattices, dedup, failed)
         keep = np.flatnonzero(reports["dedup"].representative).tolist()
     elif failed is not None:
         keep = np.flatnonzero(~failed).tolist()

@@ -686,7 +686,10 @@ class Chemeleon(nn.Module):
         the whole report is kept as self.last_dedup. With screen= as well the screen runs first and its failures
         take no part: they are neither returned nor representatives. Like the screen it is for finished
         structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
-        rank.
+        rank. dedup=MatchDedup(...) (chemeleon_amd.match_group) takes the same place with another criterion: two
+        structures are the same crystal when they match within ltol / stol / angle_tol (the definition of
+        match=), and info["dedup"] also carries "rms" against the group's representative; the report
+        (self.last_dedup) is then a MatchGroupReport.
 
         cell=Cell(...) (chemeleon_amd.cell): the lattice of every finished structure is Niggli-reduced and its
         lattice system found on the device, after the screen and before the grouping; each returned structure
@@ -739,10 +742,16 @@ class Chemeleon(nn.Module):
             cell.codes_for(n_samples)  # (a per-crystal list of the wrong length fails before sampling)
         if dedup is not None:
             from chemeleon_amd.dedup import Dedup
-            if not isinstance(dedup, Dedup):
-                raise ValueError("dedup must be a chemeleon_amd.Dedup")
+            from chemeleon_amd.match_group import MatchDedup
+            if not isinstance(dedup, (Dedup, MatchDedup)):
+                raise ValueError("dedup must be a chemeleon_amd.Dedup or a chemeleon_amd.MatchDedup")
             if stream or return_trajectory:
                 raise ValueError("dedup= applies to finished structures: not with stream / return_trajectory")
+            if isinstance(dedup, MatchDedup):
+                from chemeleon_amd.match import MAX_ATOMS as MATCH_MAX_ATOMS
+                if n_atoms > MATCH_MAX_ATOMS:
+                    raise ValueError(f"dedup=MatchDedup holds at most {MATCH_MAX_ATOMS} atoms per crystal, got "
+                                     f"n_atoms={n_atoms}")
         if screen is not None:
             from chemeleon_amd.screening import Screen
             if not isinstance(screen, Screen):

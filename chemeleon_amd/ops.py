@@ -8,6 +8,8 @@
     sched = ops.schedule(chemeleon, step_lr=1e-5)          # torch.classes.chemeleon.Schedule
     torch.ops.chemeleon.sample_step(batch, sched, t, 2.0, a, x, lat, cond, null, None, None, None, None, 0, 0, 0)
 
+    group, count, records, pairs = torch.ops.chemeleon.match_group(a, x, lat, natoms, None, 0.2, 0.3, 5.0)
+
 The classes own the library's objects (reference-counted: a Batch holds its Model, a Schedule its
 tables), so TorchScript and C++ callers build and drive the sampler with no ctypes object in sight.
 The ops launch on the current HIP stream of the batch's device under a device guard for it, refuse

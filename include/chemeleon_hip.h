@@ -1097,6 +1097,73 @@ int chm_match_run(const chm_match* plan, const void* d_cell_records, size_t n_re
                   float ltol, float stol, float angle_tol, void* d_out, size_t n_out_bytes, int32_t* d_perm,
                   int64_t n_perm, void* stream);
 
+/* Grouping duplicate structures of one batch by pairwise matching on the device: the uniqueness step of the
+ * reference's workflows (StructureMatcher().group_structures in test_unique of scripts/evaluate.py and in
+ * scripts/navigate_chemical_system.py) with the match criterion above instead of the fingerprints of chm_dedup_*.
+ * This is NOT a port of pymatgen, and how far the groups agree with group_structures has not been measured.
+ *
+ * Pairs. Every pair (h, g), h < g, of crystals with equal atom counts is one match: crystal h is the reference
+ * side (the possible leader), crystal g the sample side, both read from the same state and the same
+ * chm_cell_records. The definition of a match is chm_match_*'s, word for word (the reduced frames of both, the
+ * volume scaling, the mappings within ltol / angle_tol in ascending index capped at 256, the anchors of the rarest
+ * species, nearest-partner pairing within stol l, the mean-removed rms with the smallest winning, and the flags
+ * CHM_MATCH_NO_LATTICE, COMPOSITION, THIN and MANY_MAPPINGS): the same device code. Pairs of unequal atom counts
+ * can never match (CHM_MATCH_SIZE) and are not launched: there is no reduction to a primitive cell, so a
+ * supercell is never grouped with its primitive cell. The pairs are ordered by g, then by h;
+ * chm_match_group_num_pairs gives their number P. A pair's record {rms, max_dist, flags, matched} (16 bytes)
+ * depends on the two crystals and the tolerances alone, not on the batch, the order of the pairs or the run. A
+ * pair with an excluded crystal (d_exclude[g] != 0; NULL with n_exclude = 0: none) has flags
+ * CHM_MATCH_EXCLUDED, one with a crystal whose cell record has CHM_CELL_NOT_REDUCED, DEGENERATE or NONFINITE has
+ * CHM_MATCH_NO_LATTICE, and neither is searched (everything else 0). The relation is not symmetric in general:
+ * THIN and l are taken from the reference side h.
+ *
+ * Groups: the leader rule of chm_dedup_group on the matrix "h < g and (h, g) matched" (the same kernel). In index
+ * order a crystal is a representative when it matches no earlier representative, else it joins the earliest
+ * earlier representative it matches; the rule is not transitive, on purpose. group[g] = the representative's
+ * index (its own for a representative), count[g] = the group's size at a representative and 0 elsewhere. An
+ * excluded crystal or one without a reduced cell gets group -1: it is never a leader and nothing joins it. A
+ * leader whose pairs all carry a flag (CHM_MATCH_THIN, say) stays a group of its own.
+ *
+ * Output per crystal (32 bytes): the record of its pair with its leader and ref = the leader, pair = that pair's
+ * position; a leader has rms = max_dist = 0, flags = 0, matched = 0, ref = pair = -1; a crystal of group -1 the
+ * same with flags CHM_MATCH_EXCLUDED and / or CHM_MATCH_NO_LATTICE.
+ *
+ * The plan is built on the host from natoms alone and holds the node offsets and the pair table on the current
+ * device; a crystal of more than 256 atoms, or more than 2^31 - 1 pairs (one 1-D grid), is refused at create with
+ * CHM_E_UNSUPPORTED. The run takes every buffer with its count (cell records 128, out 32 bytes per crystal, pair
+ * records 16 bytes per pair, NULL with 0 bytes when P = 0; all 16-byte aligned; the workspace at least
+ * chm_match_group_workspace_bytes); a NULL pointer, a mismatched count or a tolerance outside chm_match_run's
+ * ranges return CHM_E_ARG naming the argument before the first HIP call and nothing is enqueued. It enqueues
+ * four kernels (the first clears the bit matrix), uses integer atomics only, allocates nothing and does not
+ * synchronise: legal under stream capture. */
+#define CHM_MATCH_EXCLUDED 64 /* chm_match_group_*: a crystal of the pair (or the crystal) is excluded */
+typedef struct {
+  float rms;       /* of the winner, in units of l of crystal h */
+  float max_dist;  /* of the winner (A) */
+  int32_t flags;   /* CHM_MATCH_* bits */
+  int32_t matched; /* 1 or 0 */
+} chm_match_pair_record; /* 16 bytes */
+typedef struct {
+  float rms;           /* of the crystal against its leader; 0 for a leader */
+  float max_dist;
+  int32_t flags;
+  int32_t matched;     /* 1 for a member, 0 for a leader and for group -1 */
+  int32_t ref;         /* the leader, or -1 */
+  int32_t pair;        /* the position of (leader, crystal) among the pairs, or -1 */
+  int32_t reserved[2]; /* written as 0 */
+} chm_match_group_record; /* 32 bytes */
+typedef struct chm_match_group chm_match_group;
+int chm_match_group_create(const int32_t* h_natoms, int num_graphs, chm_match_group** out);
+void chm_match_group_destroy(chm_match_group* plan);
+int64_t chm_match_group_num_pairs(const chm_match_group* plan);
+size_t chm_match_group_workspace_bytes(const chm_match_group* plan);
+int chm_match_group_run(const chm_match_group* plan, const void* d_cell_records, size_t n_record_bytes,
+                        const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                        const float* d_lattices, int64_t n_lattices, const uint8_t* d_exclude, int64_t n_exclude,
+                        float ltol, float stol, float angle_tol, int32_t* d_group, int64_t n_group, int32_t* d_count,
+                        int64_t n_count, void* d_out, size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes,
+                        void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
