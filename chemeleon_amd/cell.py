@@ -20,15 +20,13 @@ on real samples has not been measured; the crystal system with the atoms is chem
 ("Lattice system and reduced cell").
 """
 
-import ctypes
-import threading
-from collections import OrderedDict
 from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from chemeleon_amd import _lib
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state
 
 SYSTEMS = ("triclinic", "monoclinic", "orthorhombic", "tetragonal", "rhombohedral", "hexagonal", "cubic")
 AMBIGUOUS, MISMATCH, NOT_REDUCED, DEGENERATE, NONFINITE = 1, 2, 4, 8, 16
@@ -130,17 +128,10 @@ class CellReport:
                 "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit], "valid": bool(self.valid[g])}
 
 
-class CellPlan:
+class CellPlan(Plan):
     """Owns a chm_cell: the node offsets of one crystal list on one device."""
 
-    def __init__(self, natoms: Sequence[int], device):
-        self.natoms = tuple(int(n) for n in natoms)
-        self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().chm_cell_create(nat, len(self.natoms), ctypes.byref(h)), "chm_cell_create")
-        self.handle = h
+    _create, _destroy = "chm_cell_create", "chm_cell_destroy"
 
     def run(self, lattices, require, symprec: float, angle_tolerance: float, out):
         """Enqueues the classification on the current stream of the plan's device; `out` is a uint8 device tensor
@@ -160,33 +151,13 @@ class CellPlan:
             lattices_out.numel(), _lib.stream_handle(self.device)), "chm_cell_apply")
         return frac_out, lattices_out
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_cell_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, CellPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(CellPlan)
 
 
 def cell_plan(natoms: Sequence[int], device) -> CellPlan:
     """The plan of this crystal list on this device, cached per (natoms, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = CellPlan(key[0], dev)
-        return p
+    return _plans.get(device, natoms)
 
 
 def _need_cell(cell) -> Cell:
@@ -199,20 +170,9 @@ def _need_cell(cell) -> Cell:
 
 def _run(natoms, atom_types, frac_coords, lattices, cell, reduce):
     cell = _need_cell(cell)
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    N, B = sum(nat), len(nat)
-    codes = cell.codes_for(B)
-    if (atom_types is not None and tuple(atom_types.shape) != (N,)) or tuple(frac_coords.shape) != (N, 3) or \
-            tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be frac_coords / lattices float32")
-    dev = frac_coords.device
-    if lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
+    nat = check_natoms(natoms)
+    codes = cell.codes_for(len(nat))
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices, types_used=False)
     plan = cell_plan(nat, dev)
     x_out = lat_out = None
     with torch.cuda.device(dev):

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "chm_host.h"
+#include "plan_common.h"
 #include "cell_shared.h"
 
 // Every product and sum is rounded on its own, in fp32 and in fp64, so that the record is the same expression on
@@ -316,78 +317,34 @@ __global__ __launch_bounds__(kBlock) void k_cell_apply(ApplyArgs p) {
 
 }  // namespace
 
-struct chm_cell {
-  int B = 0;
-  long N = 0;
-  int* d_off = nullptr;  // [B + 1] first node of each crystal
-};
+struct chm_cell : chm::NodePlan {};
 
 extern "C" int chm_cell_create(const int32_t* h_natoms, int num_graphs, chm_cell** out) {
   static_assert(sizeof(chm_cell_record) == 128, "the record is 128 bytes");
-  if (!out) return fail(CHM_E_ARG, "out is NULL");
-  *out = nullptr;
-  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
-  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
-  std::vector<int> offs((size_t)num_graphs + 1, 0);
-  long N = 0;
-  for (int g = 0; g < num_graphs; ++g) {
-    if (h_natoms[g] <= 0) return fail(CHM_E_ARG, "natoms[" + std::to_string(g) + "] must be >= 1");
-    N += h_natoms[g];
-    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one cell plan");
-    offs[(size_t)g + 1] = (int)N;
-  }
-  chm_cell* p = new chm_cell;
-  p->B = num_graphs;
-  p->N = N;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_off, offs.size() * sizeof(int))) == hipSuccess)
-    e = hipMemcpy(p->d_off, offs.data(), offs.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_off) (void)hipFree(p->d_off);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_cell_create: ") + hipGetErrorString(e));
-  }
-  *out = p;
-  return CHM_OK;
+  return chm::node_plan_create(h_natoms, num_graphs, {"cell plan"}, "chm_cell_create", out);
 }
 
-extern "C" void chm_cell_destroy(chm_cell* p) {
-  if (!p) return;
-  (void)hipFree(p->d_off);
-  delete p;
-}
+extern "C" void chm_cell_destroy(chm_cell* p) { chm::node_plan_destroy(p); }
 
 namespace {
-int want(const void* ptr, long n, long expect, const char* name, const char* unit) {
-  if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
-  if (n != expect)
-    return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the cell plan needs " +
-                               std::to_string(expect));
-  return CHM_OK;
-}
+const chm::Check check{"the cell plan"};
 }  // namespace
 
 extern "C" int chm_cell_run(const chm_cell* p, const float* d_lattices, int64_t n_lattices, const int32_t* d_require,
                             int64_t n_require, float symprec, float angle_tolerance, void* d_out,
                             size_t n_out_bytes, void* stream) {
   if (!p) return fail(CHM_E_ARG, "cell plan is NULL");
-  int rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if (!d_require && n_require != 0)
-    return fail(CHM_E_ARG, "require is NULL but " + std::to_string(n_require) + " elements");
-  if (d_require && n_require != 1 && n_require != p->B)
-    return fail(CHM_E_ARG, "require: " + std::to_string(n_require) + " elements, the cell plan needs 1 (one for all) or " +
-                               std::to_string(p->B) + " ([B])");
-  if (!(symprec > 0.f && symprec <= CHM_CELL_MAX_SYMPREC))
-    return fail(CHM_E_ARG, "symprec must be in (0, 1] A");
-  if (!(angle_tolerance > 0.f && angle_tolerance <= CHM_CELL_MAX_ANGLE_TOLERANCE))
-    return fail(CHM_E_ARG, "angle_tolerance must be in (0, 30] degrees");
-  if ((rc = want(d_out, (long)n_out_bytes, 128L * p->B, "out", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
+  int rc, require_stride;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.broadcast(d_require, n_require, 1, p->B, "require", "[B]", &require_stride))) return rc;
+  if ((rc = check.range(symprec, CHM_CELL_MAX_SYMPREC, "symprec", " A"))) return rc;
+  if ((rc = check.range(angle_tolerance, CHM_CELL_MAX_ANGLE_TOLERANCE, "angle_tolerance", " degrees"))) return rc;
+  if ((rc = check.count(d_out, (long)n_out_bytes, 128L * p->B, "out", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_out, "out"))) return rc;
   CellArgs a;
   a.lat = d_lattices;
   a.require = d_require;
-  a.require_stride = (d_require && n_require == p->B && p->B > 1) ? 1 : 0;
+  a.require_stride = require_stride;
   a.symprec = symprec;
   a.angle_tolerance = angle_tolerance;
   a.out = static_cast<chm_cell_record*>(d_out);
@@ -401,12 +358,12 @@ extern "C" int chm_cell_apply(const chm_cell* p, const void* d_records, size_t n
                               int64_t n_frac_out, float* d_lattices_out, int64_t n_lattices_out, void* stream) {
   if (!p) return fail(CHM_E_ARG, "cell plan is NULL");
   int rc;
-  if ((rc = want(d_records, (long)n_record_bytes, 128L * p->B, "records", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_records) % 16) return fail(CHM_E_ARG, "records must be 16-byte aligned");
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if ((rc = want(d_frac_out, n_frac_out, 3 * p->N, "frac_out [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices_out, n_lattices_out, 9L * p->B, "lattices_out [B,3,3]", "elements"))) return rc;
+  if ((rc = check.count(d_records, (long)n_record_bytes, 128L * p->B, "records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_records, "records"))) return rc;
+  if ((rc = check.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.count(d_frac_out, n_frac_out, 3 * p->N, "frac_out [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices_out, n_lattices_out, 9L * p->B, "lattices_out [B,3,3]"))) return rc;
   if (d_frac_out == d_frac) return fail(CHM_E_ARG, "frac_out must not be frac: the cell is never applied in place");
   if (d_lattices_out == d_lattices)
     return fail(CHM_E_ARG, "lattices_out must not be lattices: the cell is never applied in place");

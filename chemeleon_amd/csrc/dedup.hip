@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "chm_host.h"
+#include "plan_common.h"
 
 // fp32 with every product and sum rounded on its own (screen.hip, constrain.hip): the fingerprint is the same
 // expression on every build
@@ -358,54 +359,16 @@ hipError_t chm::dedup_lead(int B, int W, const unsigned* match, const int* flags
   return hipGetLastError();
 }
 
-struct chm_dedup {
-  int B = 0;
-  long N = 0;
-  int* d_off = nullptr;  // [B + 1] first node of each crystal
-};
+struct chm_dedup : chm::NodePlan {};
 
 extern "C" int chm_dedup_create(const int32_t* h_natoms, int num_graphs, chm_dedup** out) {
-  if (!out) return fail(CHM_E_ARG, "out is NULL");
-  *out = nullptr;
-  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
-  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
-  std::vector<int> offs((size_t)num_graphs + 1, 0);
-  long N = 0;
-  for (int g = 0; g < num_graphs; ++g) {
-    if (h_natoms[g] <= 0) return fail(CHM_E_ARG, "natoms[" + std::to_string(g) + "] must be >= 1");
-    N += h_natoms[g];
-    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one dedup plan");
-    offs[(size_t)g + 1] = (int)N;
-  }
-  chm_dedup* p = new chm_dedup;
-  p->B = num_graphs;
-  p->N = N;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_off, offs.size() * sizeof(int))) == hipSuccess)
-    e = hipMemcpy(p->d_off, offs.data(), offs.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_off) (void)hipFree(p->d_off);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_dedup_create: ") + hipGetErrorString(e));
-  }
-  *out = p;
-  return CHM_OK;
+  return chm::node_plan_create(h_natoms, num_graphs, {"dedup plan"}, "chm_dedup_create", out);
 }
 
-extern "C" void chm_dedup_destroy(chm_dedup* p) {
-  if (!p) return;
-  (void)hipFree(p->d_off);
-  delete p;
-}
+extern "C" void chm_dedup_destroy(chm_dedup* p) { chm::node_plan_destroy(p); }
 
 namespace {
-int want(const void* ptr, long n, long expect, const char* name, const char* unit = "elements") {
-  if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
-  if (n != expect)
-    return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the dedup needs " +
-                               std::to_string(expect));
-  return CHM_OK;
-}
+const chm::Check check{"the dedup"};
 int want_bins(int K) {
   if (K < kMinBins || K > kMaxBins)
     return fail(CHM_E_ARG, "K (bins per channel) must be in [8, 256], got " + std::to_string(K));
@@ -422,12 +385,12 @@ extern "C" int chm_dedup_fingerprint(const chm_dedup* p, const int64_t* d_atom_t
   if (!positive_finite(r_cut)) return fail(CHM_E_ARG, "r_cut must be positive and finite");
   if (!positive_finite(sigma)) return fail(CHM_E_ARG, "sigma must be positive and finite");
   if (!p) return fail(CHM_E_ARG, "dedup plan is NULL");
-  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
-  if ((rc = want(d_fp, n_fp, 2L * K * p->B, "fp [B,2K]"))) return rc;
-  if ((rc = want(d_counts, n_counts, (long)kClasses * p->B, "counts [B,104]"))) return rc;
-  if ((rc = want(d_flags, n_flags, p->B, "flags [B]"))) return rc;
+  if ((rc = check.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = check.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.count(d_fp, n_fp, 2L * K * p->B, "fp [B,2K]"))) return rc;
+  if ((rc = check.count(d_counts, n_counts, (long)kClasses * p->B, "counts [B,104]"))) return rc;
+  if ((rc = check.count(d_flags, n_flags, p->B, "flags [B]"))) return rc;
   FpArgs a;
   a.a = reinterpret_cast<const long*>(d_atom_types);
   a.x = d_frac;
@@ -460,20 +423,13 @@ extern "C" int chm_dedup_group(int64_t B, int K, const float* d_fp, int64_t n_fp
   int rc;
   if ((rc = want_bins(K))) return rc;
   if (!positive_finite(tol)) return fail(CHM_E_ARG, "tol must be positive and finite");
-  if ((rc = want(d_fp, n_fp, 2L * K * B, "fp [B,2K]"))) return rc;
-  if ((rc = want(d_counts, n_counts, (long)kClasses * B, "counts [B,104]"))) return rc;
-  if (!d_flags && n_flags != 0) return fail(CHM_E_ARG, "flags is NULL but " + std::to_string(n_flags) + " elements");
-  if (d_flags && (rc = want(d_flags, n_flags, B, "flags [B]"))) return rc;
-  if (!d_exclude && n_exclude != 0)
-    return fail(CHM_E_ARG, "exclude is NULL but " + std::to_string(n_exclude) + " elements");
-  if (d_exclude && (rc = want(d_exclude, n_exclude, B, "exclude [B]"))) return rc;
-  if ((rc = want(d_group, n_group, B, "group [B]"))) return rc;
-  if ((rc = want(d_count, n_count, B, "count [B]"))) return rc;
-  if (!d_workspace) return fail(CHM_E_ARG, "workspace is NULL");
-  const size_t need = chm_dedup_workspace_bytes(B);
-  if (workspace_bytes < need)
-    return fail(CHM_E_ARG, "workspace: " + std::to_string(workspace_bytes) + " bytes, the dedup needs " +
-                               std::to_string(need));
+  if ((rc = check.count(d_fp, n_fp, 2L * K * B, "fp [B,2K]"))) return rc;
+  if ((rc = check.count(d_counts, n_counts, (long)kClasses * B, "counts [B,104]"))) return rc;
+  if ((rc = check.optional(d_flags, n_flags, B, "flags [B]"))) return rc;
+  if ((rc = check.optional(d_exclude, n_exclude, B, "exclude [B]"))) return rc;
+  if ((rc = check.count(d_group, n_group, B, "group [B]"))) return rc;
+  if ((rc = check.count(d_count, n_count, B, "count [B]"))) return rc;
+  if ((rc = check.workspace(d_workspace, workspace_bytes, chm_dedup_workspace_bytes(B)))) return rc;
   if (reinterpret_cast<uintptr_t>(d_workspace) % 4) return fail(CHM_E_ARG, "workspace must be 4-byte aligned");
   const int W = (int)((B + 31) / 32);
   unsigned* match = static_cast<unsigned*>(d_workspace);

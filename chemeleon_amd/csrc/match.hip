@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "chm_host.h"
+#include "plan_common.h"
 #include "cell_shared.h"
 
 // Every product and sum is rounded on its own (as in cell.hip).
@@ -492,21 +493,8 @@ struct chm_match {
 };
 
 namespace {
-int offsets(const int32_t* nat, int count, const char* what, std::vector<int>& offs, long* total) {
-  offs.assign((size_t)count + 1, 0);
-  long N = 0;
-  for (int g = 0; g < count; ++g) {
-    if (nat[g] <= 0) return fail(CHM_E_ARG, std::string(what) + "[" + std::to_string(g) + "] must be >= 1");
-    if (nat[g] > kMaxAtoms)
-      return fail(CHM_E_UNSUPPORTED, std::string(what) + "[" + std::to_string(g) + "] = " + std::to_string(nat[g]) +
-                                         ": the matcher holds at most " + std::to_string(kMaxAtoms) + " atoms per crystal");
-    N += nat[g];
-    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one match plan");
-    offs[(size_t)g + 1] = (int)N;
-  }
-  *total = N;
-  return CHM_OK;
-}
+const chm::OffsetRule kLists{"match plan", kMaxAtoms, "the matcher"};
+const chm::Check check{"the match plan"};
 }  // namespace
 
 extern "C" int chm_match_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms, int num_refs,
@@ -522,8 +510,8 @@ extern "C" int chm_match_create(const int32_t* h_natoms, int num_graphs, const i
   std::vector<int> offs, roffs;
   long N = 0, NR = 0;
   int rc;
-  if ((rc = offsets(h_natoms, num_graphs, "natoms", offs, &N))) return rc;
-  if ((rc = offsets(h_ref_natoms, num_refs, "ref_natoms", roffs, &NR))) return rc;
+  if ((rc = chm::node_offsets(h_natoms, num_graphs, "natoms", kLists, offs, &N))) return rc;
+  if ((rc = chm::node_offsets(h_ref_natoms, num_refs, "ref_natoms", kLists, roffs, &NR))) return rc;
   for (int g = 0; g < num_graphs; ++g)
     if (h_ref_of[g] < -1 || h_ref_of[g] >= num_refs)
       return fail(CHM_E_ARG, "ref_of[" + std::to_string(g) + "] = " + std::to_string(h_ref_of[g]) + " outside [-1, " +
@@ -531,16 +519,11 @@ extern "C" int chm_match_create(const int32_t* h_natoms, int num_graphs, const i
   std::vector<int> all(offs);
   all.insert(all.end(), roffs.begin(), roffs.end());
   all.insert(all.end(), h_ref_of, h_ref_of + num_graphs);
+  void* d_ints = nullptr;
+  if ((rc = chm::upload(all.data(), all.size() * sizeof(int), "chm_match_create", &d_ints))) return rc;
   chm_match* p = new chm_match;
   p->B = num_graphs, p->R = num_refs, p->N = N, p->NR = NR;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_ints, all.size() * sizeof(int))) == hipSuccess)
-    e = hipMemcpy(p->d_ints, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_ints) (void)hipFree(p->d_ints);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_match_create: ") + hipGetErrorString(e));
-  }
+  p->d_ints = static_cast<int*>(d_ints);
   p->d_off = p->d_ints;
   p->d_roff = p->d_off + offs.size();
   p->d_ref_of = p->d_roff + roffs.size();
@@ -554,16 +537,6 @@ extern "C" void chm_match_destroy(chm_match* p) {
   delete p;
 }
 
-namespace {
-int want(const void* ptr, long n, long expect, const char* name, const char* unit) {
-  if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
-  if (n != expect)
-    return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the match plan needs " +
-                               std::to_string(expect));
-  return CHM_OK;
-}
-}  // namespace
-
 extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, size_t n_record_bytes,
                              const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
                              const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
@@ -573,25 +546,22 @@ extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, siz
                              size_t n_out_bytes, int32_t* d_perm, int64_t n_perm, void* stream) {
   if (!p) return fail(CHM_E_ARG, "match plan is NULL");
   int rc;
-  if ((rc = want(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_cell_records) % 16) return fail(CHM_E_ARG, "cell records must be 16-byte aligned");
-  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if ((rc = want(d_ref_cell_records, (long)n_ref_record_bytes, 128L * p->R, "ref cell records", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_ref_cell_records) % 16)
-    return fail(CHM_E_ARG, "ref cell records must be 16-byte aligned");
-  if ((rc = want(d_ref_atom_types, n_ref_atom_types, p->NR, "ref_atom_types [NR]", "elements"))) return rc;
-  if ((rc = want(d_ref_frac, n_ref_frac, 3 * p->NR, "ref_frac [NR,3]", "elements"))) return rc;
-  if ((rc = want(d_ref_lattices, n_ref_lattices, 9L * p->R, "ref_lattices [R,3,3]", "elements"))) return rc;
-  if (!(ltol > 0.f && ltol <= CHM_MATCH_MAX_LTOL)) return fail(CHM_E_ARG, "ltol must be in (0, 1]");
-  if (!(stol > 0.f && stol <= CHM_MATCH_MAX_STOL)) return fail(CHM_E_ARG, "stol must be in (0, 1]");
-  if (!(angle_tol > 0.f && angle_tol <= CHM_MATCH_MAX_ANGLE_TOL))
-    return fail(CHM_E_ARG, "angle_tol must be in (0, 30] degrees");
-  if ((rc = want(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
-  if (!d_perm && n_perm != 0) return fail(CHM_E_ARG, "perm is NULL but " + std::to_string(n_perm) + " elements");
-  if (d_perm && (rc = want(d_perm, n_perm, p->N, "perm [N]", "elements"))) return rc;
+  if ((rc = check.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_cell_records, "cell records"))) return rc;
+  if ((rc = check.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = check.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.count(d_ref_cell_records, (long)n_ref_record_bytes, 128L * p->R, "ref cell records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_ref_cell_records, "ref cell records"))) return rc;
+  if ((rc = check.count(d_ref_atom_types, n_ref_atom_types, p->NR, "ref_atom_types [NR]"))) return rc;
+  if ((rc = check.count(d_ref_frac, n_ref_frac, 3 * p->NR, "ref_frac [NR,3]"))) return rc;
+  if ((rc = check.count(d_ref_lattices, n_ref_lattices, 9L * p->R, "ref_lattices [R,3,3]"))) return rc;
+  if ((rc = check.range(ltol, CHM_MATCH_MAX_LTOL, "ltol", ""))) return rc;
+  if ((rc = check.range(stol, CHM_MATCH_MAX_STOL, "stol", ""))) return rc;
+  if ((rc = check.range(angle_tol, CHM_MATCH_MAX_ANGLE_TOL, "angle_tol", " degrees"))) return rc;
+  if ((rc = check.count(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_out, "out"))) return rc;
+  if ((rc = check.optional(d_perm, n_perm, p->N, "perm [N]"))) return rc;
   MatchArgs a;
   a.rec = static_cast<const chm_cell_record*>(d_cell_records);
   a.types = reinterpret_cast<const long long*>(d_atom_types);
@@ -640,7 +610,7 @@ extern "C" int chm_match_group_create(const int32_t* h_natoms, int num_graphs, c
   std::vector<int> offs;
   long N = 0;
   int rc;
-  if ((rc = offsets(h_natoms, num_graphs, "natoms", offs, &N))) return rc;
+  if ((rc = chm::node_offsets(h_natoms, num_graphs, "natoms", kLists, offs, &N))) return rc;
   const int B = num_graphs;
   // rank[g] = crystals before g with g's atom count; P = sum of the ranks, counted before anything is built
   std::vector<int> seen(kMaxAtoms + 1, 0), rank((size_t)B), first((size_t)B);
@@ -665,16 +635,11 @@ extern "C" int chm_match_group_create(const int32_t* h_natoms, int num_graphs, c
   for (int g = 0; g <= B; ++g) hi[g] = offs[g];
   for (int g = 0; g < B; ++g) hi[B + 1 + g] = first[g], hi[2 * B + 1 + g] = rank[g];
   if (P) memcpy(host.data() + ints_bytes, pairs.data(), (size_t)P * sizeof(int2));
+  void* d_mem = nullptr;
+  if ((rc = chm::upload(host.data(), host.size(), "chm_match_group_create", &d_mem))) return rc;
   chm_match_group* p = new chm_match_group;
   p->B = B, p->N = N, p->P = P;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_mem, host.size())) == hipSuccess)
-    e = hipMemcpy(p->d_mem, host.data(), host.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_mem) (void)hipFree(p->d_mem);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_match_group_create: ") + hipGetErrorString(e));
-  }
+  p->d_mem = static_cast<char*>(d_mem);
   p->d_off = reinterpret_cast<const int*>(p->d_mem);
   p->d_first = p->d_off + B + 1;
   p->d_rank = p->d_first + B;
@@ -706,34 +671,28 @@ extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_
                                    size_t workspace_bytes, void* stream) {
   if (!p) return fail(CHM_E_ARG, "match-group plan is NULL");
   int rc;
-  if ((rc = want(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_cell_records) % 16) return fail(CHM_E_ARG, "cell records must be 16-byte aligned");
-  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if (!d_exclude && n_exclude != 0)
-    return fail(CHM_E_ARG, "exclude is NULL but " + std::to_string(n_exclude) + " elements");
-  if (d_exclude && (rc = want(d_exclude, n_exclude, p->B, "exclude [B]", "elements"))) return rc;
-  if (!(ltol > 0.f && ltol <= CHM_MATCH_MAX_LTOL)) return fail(CHM_E_ARG, "ltol must be in (0, 1]");
-  if (!(stol > 0.f && stol <= CHM_MATCH_MAX_STOL)) return fail(CHM_E_ARG, "stol must be in (0, 1]");
-  if (!(angle_tol > 0.f && angle_tol <= CHM_MATCH_MAX_ANGLE_TOL))
-    return fail(CHM_E_ARG, "angle_tol must be in (0, 30] degrees");
-  if ((rc = want(d_group, n_group, p->B, "group [B]", "elements"))) return rc;
-  if ((rc = want(d_count, n_count, p->B, "count [B]", "elements"))) return rc;
-  if ((rc = want(d_out, (long)n_out_bytes, 32L * p->B, "out", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
+  if ((rc = check.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_cell_records, "cell records"))) return rc;
+  if ((rc = check.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = check.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.optional(d_exclude, n_exclude, p->B, "exclude [B]"))) return rc;
+  if ((rc = check.range(ltol, CHM_MATCH_MAX_LTOL, "ltol", ""))) return rc;
+  if ((rc = check.range(stol, CHM_MATCH_MAX_STOL, "stol", ""))) return rc;
+  if ((rc = check.range(angle_tol, CHM_MATCH_MAX_ANGLE_TOL, "angle_tol", " degrees"))) return rc;
+  if ((rc = check.count(d_group, n_group, p->B, "group [B]"))) return rc;
+  if ((rc = check.count(d_count, n_count, p->B, "count [B]"))) return rc;
+  if ((rc = check.count(d_out, (long)n_out_bytes, 32L * p->B, "out", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_out, "out"))) return rc;
   if (p->P == 0) {
     if (n_pair_bytes != 0) return fail(CHM_E_ARG, "pair records: " + std::to_string(n_pair_bytes) + " bytes, the plan has no pair");
-  } else if ((rc = want(d_pair_records, (long)n_pair_bytes, 16L * p->P, "pair records", "bytes"))) {
+  } else if ((rc = check.count(d_pair_records, (long)n_pair_bytes, 16L * p->P, "pair records", "bytes"))) {
     return rc;
   }
-  if (reinterpret_cast<uintptr_t>(d_pair_records) % 16) return fail(CHM_E_ARG, "pair records must be 16-byte aligned");
-  if (!d_workspace) return fail(CHM_E_ARG, "workspace is NULL");
-  const size_t need = chm_match_group_workspace_bytes(p);
-  if (workspace_bytes < need)
-    return fail(CHM_E_ARG, "workspace: " + std::to_string(workspace_bytes) + " bytes, the match grouping needs " +
-                               std::to_string(need));
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(CHM_E_ARG, "workspace must be 16-byte aligned");
+  if ((rc = check.aligned16(d_pair_records, "pair records"))) return rc;
+  const chm::Check grouping{"the match grouping"};
+  if ((rc = grouping.workspace(d_workspace, workspace_bytes, chm_match_group_workspace_bytes(p)))) return rc;
+  if ((rc = grouping.aligned16(d_workspace, "workspace"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int B = p->B, W = (B + 31) / 32;
   unsigned* bits = static_cast<unsigned*>(d_workspace);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "chm_host.h"
+#include "plan_common.h"
 
 // Distances are fp32 with every product and sum rounded on its own, each Cartesian component summed over
 // k = 0, 1, 2 in order, so that the record is the same expression on every build (constrain.hip explains why
@@ -227,79 +228,37 @@ __global__ __launch_bounds__(kBlock) void k_screen(ScreenArgs p) {
 
 }  // namespace
 
-struct chm_screen {
-  int B = 0;
-  long N = 0;
-  int* d_off = nullptr;  // [B + 1] first node of each crystal
-};
+struct chm_screen : chm::NodePlan {};
 
 extern "C" int chm_screen_create(const int32_t* h_natoms, int num_graphs, chm_screen** out) {
   static_assert(sizeof(chm_screen_record) == 64, "the record is 64 bytes");
-  if (!out) return fail(CHM_E_ARG, "out is NULL");
-  *out = nullptr;
-  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
-  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
-  std::vector<int> offs((size_t)num_graphs + 1, 0);
-  long N = 0;
-  for (int g = 0; g < num_graphs; ++g) {
-    if (h_natoms[g] <= 0) return fail(CHM_E_ARG, "natoms[" + std::to_string(g) + "] must be >= 1");
-    N += h_natoms[g];
-    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one screen");
-    offs[(size_t)g + 1] = (int)N;
-  }
-  chm_screen* p = new chm_screen;
-  p->B = num_graphs;
-  p->N = N;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_off, offs.size() * sizeof(int))) == hipSuccess)
-    e = hipMemcpy(p->d_off, offs.data(), offs.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_off) (void)hipFree(p->d_off);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_screen_create: ") + hipGetErrorString(e));
-  }
-  *out = p;
-  return CHM_OK;
+  return chm::node_plan_create(h_natoms, num_graphs, {"screen"}, "chm_screen_create", out);
 }
 
-extern "C" void chm_screen_destroy(chm_screen* p) {
-  if (!p) return;
-  (void)hipFree(p->d_off);
-  delete p;
-}
+extern "C" void chm_screen_destroy(chm_screen* p) { chm::node_plan_destroy(p); }
 
 extern "C" int chm_screen_run(const chm_screen* p, const int64_t* d_atom_types, int64_t n_atom_types,
                               const float* d_frac, int64_t n_frac, const float* d_lattices, int64_t n_lattices,
                               const int32_t* d_target, int64_t n_target, float max_length, float min_distance,
                               void* d_out, size_t n_out_bytes, void* stream) {
   if (!p) return fail(CHM_E_ARG, "screen plan is NULL");
-  auto want = [&](const void* ptr, long n, long expect, const char* name, const char* unit) -> int {
-    if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
-    if (n != expect)
-      return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the screen needs " +
-                                 std::to_string(expect));
-    return CHM_OK;
-  };
-  int rc;
-  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if (!d_target && n_target != 0) return fail(CHM_E_ARG, "target is NULL but " + std::to_string(n_target) + " elements");
-  if (d_target && n_target != kClasses && n_target != (long)kClasses * p->B)
-    return fail(CHM_E_ARG, "target: " + std::to_string(n_target) + " elements, the screen needs " +
-                               std::to_string(kClasses) + " (one for all) or " +
-                               std::to_string((long)kClasses * p->B) + " ([B,104])");
+  const chm::Check c{"the screen"};
+  int rc, target_stride;
+  if ((rc = c.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = c.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = c.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = c.broadcast(d_target, n_target, kClasses, p->B, "target", "[B,104]", &target_stride))) return rc;
   if (!(max_length > 0.f)) return fail(CHM_E_ARG, "max_length must be > 0");
   if (!(min_distance > 0.f)) return fail(CHM_E_ARG, "min_distance must be > 0");
-  if ((rc = want(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
+  if ((rc = c.count(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
+  if ((rc = c.aligned16(d_out, "out"))) return rc;
   ScreenArgs a;
   a.a = reinterpret_cast<const long*>(d_atom_types);
   a.x = d_frac;
   a.lat = d_lattices;
   a.off = p->d_off;
   a.target = d_target;
-  a.target_stride = (d_target && n_target == (long)kClasses * p->B) ? kClasses : 0;
+  a.target_stride = target_stride;
   a.max_length = max_length;
   a.min_distance = min_distance;
   a.out = static_cast<chm_screen_record*>(d_out);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "chm_host.h"
+#include "plan_common.h"
 #include "cell_shared.h"
 
 // Every product and sum is rounded on its own (as in cell.hip).
@@ -288,60 +289,15 @@ __global__ __launch_bounds__(kBlock) void k_symm(SymmArgs p) {
 
 }  // namespace
 
-struct chm_symm {
-  int B = 0;
-  long N = 0;
-  int* d_off = nullptr;  // [B + 1] first node of each crystal
-};
+struct chm_symm : chm::NodePlan {};
 
 extern "C" int chm_symm_create(const int32_t* h_natoms, int num_graphs, chm_symm** out) {
   static_assert(sizeof(chm_symm_record) == 64, "the record is 64 bytes");
-  if (!out) return fail(CHM_E_ARG, "out is NULL");
-  *out = nullptr;
-  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
-  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
-  std::vector<int> offs((size_t)num_graphs + 1, 0);
-  long N = 0;
-  for (int g = 0; g < num_graphs; ++g) {
-    if (h_natoms[g] <= 0) return fail(CHM_E_ARG, "natoms[" + std::to_string(g) + "] must be >= 1");
-    if (h_natoms[g] > kMaxAtoms)
-      return fail(CHM_E_UNSUPPORTED, "natoms[" + std::to_string(g) + "] = " + std::to_string(h_natoms[g]) +
-                                         ": the symmetry search holds at most " + std::to_string(kMaxAtoms) +
-                                         " atoms per crystal");
-    N += h_natoms[g];
-    if (N > INT32_MAX) return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 atoms in one symmetry plan");
-    offs[(size_t)g + 1] = (int)N;
-  }
-  chm_symm* p = new chm_symm;
-  p->B = num_graphs;
-  p->N = N;
-  hipError_t e;
-  if ((e = hipMalloc((void**)&p->d_off, offs.size() * sizeof(int))) == hipSuccess)
-    e = hipMemcpy(p->d_off, offs.data(), offs.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (p->d_off) (void)hipFree(p->d_off);
-    delete p;
-    return fail(CHM_E_HIP, std::string("chm_symm_create: ") + hipGetErrorString(e));
-  }
-  *out = p;
-  return CHM_OK;
+  return chm::node_plan_create(h_natoms, num_graphs, {"symmetry plan", kMaxAtoms, "the symmetry search"},
+                               "chm_symm_create", out);
 }
 
-extern "C" void chm_symm_destroy(chm_symm* p) {
-  if (!p) return;
-  (void)hipFree(p->d_off);
-  delete p;
-}
-
-namespace {
-int want(const void* ptr, long n, long expect, const char* name, const char* unit) {
-  if (!ptr) return fail(CHM_E_ARG, std::string(name) + " is NULL");
-  if (n != expect)
-    return fail(CHM_E_ARG, std::string(name) + ": " + std::to_string(n) + " " + unit + ", the symmetry plan needs " +
-                               std::to_string(expect));
-  return CHM_OK;
-}
-}  // namespace
+extern "C" void chm_symm_destroy(chm_symm* p) { chm::node_plan_destroy(p); }
 
 extern "C" int chm_symm_run(const chm_symm* p, const void* d_cell_records, size_t n_record_bytes,
                             const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
@@ -349,29 +305,20 @@ extern "C" int chm_symm_run(const chm_symm* p, const void* d_cell_records, size_
                             float symprec, float angle_tolerance, void* d_out, size_t n_out_bytes, void* d_ops,
                             size_t n_ops_bytes, void* stream) {
   if (!p) return fail(CHM_E_ARG, "symmetry plan is NULL");
-  int rc;
-  if ((rc = want(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_cell_records) % 16) return fail(CHM_E_ARG, "cell records must be 16-byte aligned");
-  if ((rc = want(d_atom_types, n_atom_types, p->N, "atom_types [N]", "elements"))) return rc;
-  if ((rc = want(d_frac, n_frac, 3 * p->N, "frac [N,3]", "elements"))) return rc;
-  if ((rc = want(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]", "elements"))) return rc;
-  if (!d_require && n_require != 0)
-    return fail(CHM_E_ARG, "require is NULL but " + std::to_string(n_require) + " elements");
-  if (d_require && n_require != 1 && n_require != p->B)
-    return fail(CHM_E_ARG, "require: " + std::to_string(n_require) + " elements, the symmetry plan needs 1 (one for all) or " +
-                               std::to_string(p->B) + " ([B])");
-  if (!(symprec > 0.f && symprec <= CHM_CELL_MAX_SYMPREC))
-    return fail(CHM_E_ARG, "symprec must be in (0, 1] A");
-  if (!(angle_tolerance > 0.f && angle_tolerance <= CHM_CELL_MAX_ANGLE_TOLERANCE))
-    return fail(CHM_E_ARG, "angle_tolerance must be in (0, 30] degrees");
-  if ((rc = want(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % 16) return fail(CHM_E_ARG, "out must be 16-byte aligned");
-  if (!d_ops && n_ops_bytes != 0)
-    return fail(CHM_E_ARG, "ops is NULL but " + std::to_string(n_ops_bytes) + " bytes");
-  if (d_ops) {
-    if ((rc = want(d_ops, (long)n_ops_bytes, 16L * kMaxOps * p->B, "ops", "bytes"))) return rc;
-    if (reinterpret_cast<uintptr_t>(d_ops) % 16) return fail(CHM_E_ARG, "ops must be 16-byte aligned");
-  }
+  const chm::Check c{"the symmetry plan"};
+  int rc, require_stride;
+  if ((rc = c.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if ((rc = c.aligned16(d_cell_records, "cell records"))) return rc;
+  if ((rc = c.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = c.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = c.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = c.broadcast(d_require, n_require, 1, p->B, "require", "[B]", &require_stride))) return rc;
+  if ((rc = c.range(symprec, CHM_CELL_MAX_SYMPREC, "symprec", " A"))) return rc;
+  if ((rc = c.range(angle_tolerance, CHM_CELL_MAX_ANGLE_TOLERANCE, "angle_tolerance", " degrees"))) return rc;
+  if ((rc = c.count(d_out, (long)n_out_bytes, 64L * p->B, "out", "bytes"))) return rc;
+  if ((rc = c.aligned16(d_out, "out"))) return rc;
+  if ((rc = c.optional(d_ops, (long)n_ops_bytes, 16L * kMaxOps * p->B, "ops", "bytes"))) return rc;
+  if ((rc = c.aligned16(d_ops, "ops"))) return rc;
   SymmArgs a;
   a.rec = static_cast<const chm_cell_record*>(d_cell_records);
   a.types = reinterpret_cast<const long long*>(d_atom_types);
@@ -379,7 +326,7 @@ extern "C" int chm_symm_run(const chm_symm* p, const void* d_cell_records, size_
   a.lat = d_lattices;
   a.off = p->d_off;
   a.require = d_require;
-  a.require_stride = (d_require && n_require == p->B && p->B > 1) ? 1 : 0;
+  a.require_stride = require_stride;
   a.symprec = symprec;
   a.angle_tolerance = angle_tolerance;
   a.out = static_cast<chm_symm_record*>(d_out);

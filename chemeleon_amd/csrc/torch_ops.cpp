@@ -27,6 +27,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -328,31 +329,114 @@ at::Tensor d3pm_sample(const at::Tensor& logits, const at::Tensor& xt, const at:
   return out;
 }
 
+// ---------------------------------------------------------------- finishing legs
+// screen, dedup, cell, symmetry, match and match_group share what stands between here and the first of them:
+// the checks of a state against its crystal list, the optional exclude / require tensors, and one plan cache.
+// A cache keeps the plans of the last 8 (crystal lists, device) keys, evicts the oldest first and lives as long
+// as the process (nothing is freed during static destruction, when the HIP runtime may be gone). It hands out
+// shared_ptrs: an op holds its entry until its chm_*_run calls have returned, so an entry that another host
+// thread evicts meanwhile is destroyed after that, never under the call.
+constexpr float kMatchCellSymprec = 0.1f, kMatchCellAngleTolerance = 10.0f;  // the cell pass in front of the matcher
+
+using Lists = std::vector<std::vector<int64_t>>;  // a cache key: natoms (match: natoms, ref_natoms, ref_of)
+
+// a crystal list as the C ABI takes it; `op` and `what` word the refusal ("screen: atoms per crystal ...")
+std::vector<int32_t> to_int32(const std::vector<int64_t>& natoms, const char* op, const char* what) {
+  std::vector<int32_t> nat;
+  for (int64_t n : natoms) {
+    TORCH_CHECK(n >= 1 && n <= INT32_MAX, op, ": atoms per ", what, " must be >= 1, got ", n);
+    nat.push_back((int32_t)n);
+  }
+  return nat;
+}
+
+// a chm_* handle that is destroyed with its owner (every chm_*_destroy takes NULL)
+template <class T, void (*Destroy)(T*)>
+struct Handle {
+  T* p = nullptr;
+  Handle() = default;
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  ~Handle() { Destroy(p); }
+};
+using CellHandle = Handle<chm_cell, chm_cell_destroy>;
+
+// Entry: default-constructible, create(key) builds its handles or raises (what it had built goes with it)
+template <class Entry>
+std::shared_ptr<Entry> cached_plan(const Lists& key, int device) {
+  struct Cache {
+    std::mutex mu;
+    std::vector<std::tuple<Lists, int, std::shared_ptr<Entry>>> plans;
+  };
+  static Cache* cache = new Cache;
+  std::lock_guard<std::mutex> lk(cache->mu);
+  for (auto& e : cache->plans)
+    if (std::get<1>(e) == device && std::get<0>(e) == key) return std::get<2>(e);
+  auto entry = std::make_shared<Entry>();
+  entry->create(key);
+  if (cache->plans.size() >= 8) cache->plans.erase(cache->plans.begin());
+  cache->plans.emplace_back(key, device, entry);
+  return entry;
+}
+
+struct Crystals {
+  int64_t N, B;
+};
+
+// a state's tensors (atom_types may be absent: cell) on `dev`, then their shapes for `natoms`; `pre` = "ref_" for
+// the reference lists of match
+void need_crystals_on(const c10::Device& dev, const at::Tensor* atom_types, const at::Tensor& frac,
+                      const at::Tensor& lattices, const std::string& pre = "") {
+  if (atom_types) need_on(*atom_types, dev, at::kLong, (pre + "atom_types").c_str());
+  need_on(frac, dev, at::kFloat, (pre + "frac").c_str());
+  need_on(lattices, dev, at::kFloat, (pre + "lattices").c_str());
+}
+
+Crystals need_crystals_shape(const std::vector<int64_t>& natoms, const at::Tensor* atom_types, const at::Tensor& frac,
+                             const at::Tensor& lattices, const std::string& pre = "") {
+  int64_t N = 0;
+  for (int64_t n : natoms) N += n;
+  const int64_t B = (int64_t)natoms.size();
+  if (atom_types) need_shape(*atom_types, {N}, (pre + "atom_types").c_str());
+  need_shape(frac, {N, 3}, (pre + "frac").c_str());
+  need_shape(lattices, {B, 3, 3}, (pre + "lattices").c_str());
+  return {N, B};
+}
+
+Crystals need_crystals(const c10::Device& dev, const std::vector<int64_t>& natoms, const at::Tensor* atom_types,
+                       const at::Tensor& frac, const at::Tensor& lattices) {
+  need_crystals_on(dev, atom_types, frac, lattices);
+  return need_crystals_shape(natoms, atom_types, frac, lattices);
+}
+
+// exclude: a bool / uint8 tensor [B] of crystals that take no part, or None (NULL)
+const uint8_t* optional_exclude(const c10::optional<at::Tensor>& exclude, const c10::Device& dev, int64_t B) {
+  if (!exclude.has_value()) return nullptr;
+  TORCH_CHECK(exclude->scalar_type() == at::kBool || exclude->scalar_type() == at::kByte,
+              "exclude: expected bool or uint8, got ", exclude->scalar_type());
+  need_on(*exclude, dev, exclude->scalar_type(), "exclude");
+  need_shape(*exclude, {B}, "exclude");
+  return static_cast<const uint8_t*>(exclude->data_ptr());
+}
+
+// require: the wanted system codes, int32 [1] or [B], or None (NULL, 0)
+std::pair<const int32_t*, int64_t> optional_require(const c10::optional<at::Tensor>& require, const c10::Device& dev,
+                                                    int64_t B) {
+  if (!require.has_value()) return {nullptr, 0};
+  need_on(*require, dev, at::kInt, "require");
+  TORCH_CHECK(require->dim() == 1 && (require->size(0) == 1 || require->size(0) == B),
+              "require: expected shape [1] or [", B, "], got ", require->sizes());
+  return {require->data_ptr<int32_t>(), require->numel()};
+}
+
 // The screen of finished structures (chm_screen_run): cell parameters, the shortest periodic distance, formula
 // units and flags per crystal -> (floats [B,8] = a, b, c, alpha, beta, gamma, volume, dmin; ints [B,4] = i_min,
 // j_min, formula_units, flags). target: the wanted reduced element counts, int32 [104] or [B,104], or None.
-// Plans (node offsets on the device) are cached per (natoms, device), the last 8; the cache lives as long as
-// the process (nothing is freed during static destruction, when the HIP runtime may be gone).
-struct ScreenPlans {
-  std::mutex mu;
-  std::vector<std::tuple<std::vector<int64_t>, int, chm_screen*>> plans;
-  chm_screen* get(const std::vector<int64_t>& natoms, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
-    std::vector<int32_t> nat;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "screen: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    chm_screen* p = nullptr;
-    check(chm_screen_create(nat.data(), (int)nat.size(), &p), "chm_screen_create");
-    if (plans.size() >= 8) {
-      chm_screen_destroy(std::get<2>(plans.front()));
-      plans.erase(plans.begin());
-    }
-    plans.emplace_back(natoms, device, p);
-    return p;
+struct ScreenPlan {
+  Handle<chm_screen, chm_screen_destroy> screen;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "screen", "crystal");
+    check(chm_screen_create(nat.data(), (int)nat.size(), &screen.p), "chm_screen_create");
   }
 };
 
@@ -360,18 +444,9 @@ std::tuple<at::Tensor, at::Tensor> screen(const at::Tensor& atom_types, const at
                                           const at::Tensor& lattices, std::vector<int64_t> natoms,
                                           const c10::optional<at::Tensor>& target, double max_length,
                                           double min_distance) {
-  static ScreenPlans* cache = new ScreenPlans;
   TORCH_CHECK(!natoms.empty(), "screen: natoms is empty");
   const c10::Device dev = frac.device();
-  need_on(atom_types, dev, at::kLong, "atom_types");
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  int64_t N = 0;
-  for (int64_t n : natoms) N += n;
-  const int64_t B = (int64_t)natoms.size();
-  need_shape(atom_types, {N}, "atom_types");
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
+  const int64_t B = need_crystals(dev, natoms, &atom_types, frac, lattices).B;
   const int32_t* tg = nullptr;
   int64_t n_tg = 0;
   if (target.has_value()) {
@@ -383,39 +458,23 @@ std::tuple<at::Tensor, at::Tensor> screen(const at::Tensor& atom_types, const at
     n_tg = target->numel();
   }
   HIPGuardMasqueradingAsCUDA guard(dev);
-  chm_screen* plan = cache->get(natoms, dev.index());
+  const auto plan = cached_plan<ScreenPlan>({natoms}, dev.index());
   at::Tensor rec = at::empty({B, 64}, at::TensorOptions().dtype(at::kByte).device(dev));
-  check(chm_screen_run(plan, atom_types.data_ptr<int64_t>(), atom_types.numel(), frac.data_ptr<float>(), frac.numel(),
-                       lattices.data_ptr<float>(), lattices.numel(), tg, n_tg, (float)max_length, (float)min_distance,
-                       rec.data_ptr(), (size_t)rec.numel(), stream()),
+  check(chm_screen_run(plan->screen.p, atom_types.data_ptr<int64_t>(), atom_types.numel(), frac.data_ptr<float>(),
+                       frac.numel(), lattices.data_ptr<float>(), lattices.numel(), tg, n_tg, (float)max_length,
+                       (float)min_distance, rec.data_ptr(), (size_t)rec.numel(), stream()),
         "chm_screen_run");
   return {rec.view(at::kFloat).slice(1, 0, 8).contiguous(), rec.view(at::kInt).slice(1, 8, 12).contiguous()};
 }
 
 // Grouping of duplicate structures (chm_dedup_fingerprint + chm_dedup_group): the state's fingerprints
 // ([B, 2 * bins], include/chemeleon_hip.h) and their groups by the leader rule -> (group [B] int32: the
-// representative's index or -1, count [B] int32: the group's size at a representative, fingerprint). exclude: a
-// bool / uint8 tensor [B] of crystals that take no part, or None. Plans are cached as the screen's.
-struct DedupPlans {
-  std::mutex mu;
-  std::vector<std::tuple<std::vector<int64_t>, int, chm_dedup*>> plans;
-  chm_dedup* get(const std::vector<int64_t>& natoms, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
-    std::vector<int32_t> nat;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "dedup: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    chm_dedup* p = nullptr;
-    check(chm_dedup_create(nat.data(), (int)nat.size(), &p), "chm_dedup_create");
-    if (plans.size() >= 8) {
-      chm_dedup_destroy(std::get<2>(plans.front()));
-      plans.erase(plans.begin());
-    }
-    plans.emplace_back(natoms, device, p);
-    return p;
+// representative's index or -1, count [B] int32: the group's size at a representative, fingerprint).
+struct DedupPlan {
+  Handle<chm_dedup, chm_dedup_destroy> dedup;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "dedup", "crystal");
+    check(chm_dedup_create(nat.data(), (int)nat.size(), &dedup.p), "chm_dedup_create");
   }
 };
 
@@ -423,38 +482,23 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> dedup(const at::Tensor& atom_type
                                                      const at::Tensor& lattices, std::vector<int64_t> natoms,
                                                      const c10::optional<at::Tensor>& exclude, double tol,
                                                      double r_cut, double sigma, int64_t bins) {
-  static DedupPlans* cache = new DedupPlans;
   TORCH_CHECK(!natoms.empty(), "dedup: natoms is empty");
   TORCH_CHECK(bins >= 8 && bins <= 256, "dedup: bins must be in [8, 256], got ", bins);
   const c10::Device dev = frac.device();
-  need_on(atom_types, dev, at::kLong, "atom_types");
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  int64_t N = 0;
-  for (int64_t n : natoms) N += n;
-  const int64_t B = (int64_t)natoms.size();
-  need_shape(atom_types, {N}, "atom_types");
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
-  const uint8_t* ex = nullptr;
-  if (exclude.has_value()) {
-    TORCH_CHECK(exclude->scalar_type() == at::kBool || exclude->scalar_type() == at::kByte,
-                "exclude: expected bool or uint8, got ", exclude->scalar_type());
-    need_on(*exclude, dev, exclude->scalar_type(), "exclude");
-    need_shape(*exclude, {B}, "exclude");
-    ex = static_cast<const uint8_t*>(exclude->data_ptr());
-  }
+  const int64_t B = need_crystals(dev, natoms, &atom_types, frac, lattices).B;
+  const uint8_t* ex = optional_exclude(exclude, dev, B);
   HIPGuardMasqueradingAsCUDA guard(dev);
-  chm_dedup* plan = cache->get(natoms, dev.index());
+  const auto plan = cached_plan<DedupPlan>({natoms}, dev.index());
   const auto ints = at::TensorOptions().dtype(at::kInt).device(dev);
   at::Tensor fp = at::empty({B, 2 * bins}, frac.options()), counts = at::empty({B, 104}, ints),
              flags = at::empty({B}, ints), group = at::empty({B}, ints), count = at::empty({B}, ints);
   const size_t ws_bytes = chm_dedup_workspace_bytes(B);
   at::Tensor ws = at::empty({(int64_t)ws_bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-  check(chm_dedup_fingerprint(plan, atom_types.data_ptr<int64_t>(), atom_types.numel(), frac.data_ptr<float>(),
-                              frac.numel(), lattices.data_ptr<float>(), lattices.numel(), (int)bins, (float)r_cut,
-                              (float)sigma, fp.data_ptr<float>(), fp.numel(), counts.data_ptr<int32_t>(),
-                              counts.numel(), flags.data_ptr<int32_t>(), flags.numel(), stream()),
+  check(chm_dedup_fingerprint(plan->dedup.p, atom_types.data_ptr<int64_t>(), atom_types.numel(),
+                              frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(), lattices.numel(),
+                              (int)bins, (float)r_cut, (float)sigma, fp.data_ptr<float>(), fp.numel(),
+                              counts.data_ptr<int32_t>(), counts.numel(), flags.data_ptr<int32_t>(), flags.numel(),
+                              stream()),
         "chm_dedup_fingerprint");
   check(chm_dedup_group(B, (int)bins, fp.data_ptr<float>(), fp.numel(), counts.data_ptr<int32_t>(), counts.numel(),
                         flags.data_ptr<int32_t>(), flags.numel(), ex, ex ? B : 0, (float)tol,
@@ -467,28 +511,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> dedup(const at::Tensor& atom_type
 // Lattice system and reduced cell (chm_cell_run + chm_cell_apply): the state's cell records and the state in the
 // reduced cells -> (floats [B,8] = a, b, c, alpha, beta, gamma, volume, 0 of the reduced cell; ints [B,18] = T
 // (9, row-major), n_ops, n2, n3, n4, n6, system, halvings, flags, passes; frac [N,3] in the reduced basis;
-// lattices [B,3,3] reduced). require: the wanted system codes, int32 [1] or [B], or None. Plans are cached as
-// the screen's.
-struct CellPlans {
-  std::mutex mu;
-  std::vector<std::tuple<std::vector<int64_t>, int, chm_cell*>> plans;
-  chm_cell* get(const std::vector<int64_t>& natoms, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return std::get<2>(e);
-    std::vector<int32_t> nat;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "cell: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    chm_cell* p = nullptr;
-    check(chm_cell_create(nat.data(), (int)nat.size(), &p), "chm_cell_create");
-    if (plans.size() >= 8) {
-      chm_cell_destroy(std::get<2>(plans.front()));
-      plans.erase(plans.begin());
-    }
-    plans.emplace_back(natoms, device, p);
-    return p;
+// lattices [B,3,3] reduced).
+struct CellPlan {
+  CellHandle cells;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "cell", "crystal");
+    check(chm_cell_create(nat.data(), (int)nat.size(), &cells.p), "chm_cell_create");
   }
 };
 
@@ -496,33 +524,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> cell(const at::Tensor
                                                                 std::vector<int64_t> natoms,
                                                                 const c10::optional<at::Tensor>& require,
                                                                 double symprec, double angle_tolerance) {
-  static CellPlans* cache = new CellPlans;
   TORCH_CHECK(!natoms.empty(), "cell: natoms is empty");
   const c10::Device dev = frac.device();
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  int64_t N = 0;
-  for (int64_t n : natoms) N += n;
-  const int64_t B = (int64_t)natoms.size();
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
-  const int32_t* rq = nullptr;
-  int64_t n_rq = 0;
-  if (require.has_value()) {
-    need_on(*require, dev, at::kInt, "require");
-    TORCH_CHECK(require->dim() == 1 && (require->size(0) == 1 || require->size(0) == B),
-                "require: expected shape [1] or [", B, "], got ", require->sizes());
-    rq = require->data_ptr<int32_t>();
-    n_rq = require->numel();
-  }
+  const int64_t B = need_crystals(dev, natoms, nullptr, frac, lattices).B;
+  const auto rq = optional_require(require, dev, B);
   HIPGuardMasqueradingAsCUDA guard(dev);
-  chm_cell* plan = cache->get(natoms, dev.index());
+  const auto plan = cached_plan<CellPlan>({natoms}, dev.index());
   at::Tensor rec = at::empty({B, 128}, at::TensorOptions().dtype(at::kByte).device(dev));
   at::Tensor x_out = at::empty_like(frac), lat_out = at::empty_like(lattices);
-  check(chm_cell_run(plan, lattices.data_ptr<float>(), lattices.numel(), rq, n_rq, (float)symprec,
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), rq.first, rq.second, (float)symprec,
                      (float)angle_tolerance, rec.data_ptr(), (size_t)rec.numel(), stream()),
         "chm_cell_run");
-  check(chm_cell_apply(plan, rec.data_ptr(), (size_t)rec.numel(), frac.data_ptr<float>(), frac.numel(),
+  check(chm_cell_apply(plan->cells.p, rec.data_ptr(), (size_t)rec.numel(), frac.data_ptr<float>(), frac.numel(),
                        lattices.data_ptr<float>(), lattices.numel(), x_out.data_ptr<float>(), x_out.numel(),
                        lat_out.data_ptr<float>(), lat_out.numel(), stream()),
         "chm_cell_apply");
@@ -532,35 +545,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> cell(const at::Tensor
 
 // Crystal system with the atoms (chm_cell_run + chm_symm_run on one stream): (records uint8 [B,64] = the
 // chm_symm_record of every crystal; operations uint8 [B,48,16] = the slots of (int32 candidate index, float t[3]),
-// or [0,48,16] unless `operations`). require: the wanted crystal-system codes, int32 [1] or [B], or None. Plans
-// are cached as the screen's.
-struct SymmPlans {
-  std::mutex mu;
-  std::vector<std::tuple<std::vector<int64_t>, int, chm_cell*, chm_symm*>> plans;
-  std::pair<chm_cell*, chm_symm*> get(const std::vector<int64_t>& natoms, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (std::get<1>(e) == device && std::get<0>(e) == natoms) return {std::get<2>(e), std::get<3>(e)};
-    std::vector<int32_t> nat;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "symmetry: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    chm_symm* s = nullptr;
-    check(chm_symm_create(nat.data(), (int)nat.size(), &s), "chm_symm_create");
-    chm_cell* c = nullptr;
-    const int rc = chm_cell_create(nat.data(), (int)nat.size(), &c);
-    if (rc != CHM_OK) {
-      chm_symm_destroy(s);
-      check(rc, "chm_cell_create");
-    }
-    if (plans.size() >= 8) {
-      chm_cell_destroy(std::get<2>(plans.front()));
-      chm_symm_destroy(std::get<3>(plans.front()));
-      plans.erase(plans.begin());
-    }
-    plans.emplace_back(natoms, device, c, s);
-    return {c, s};
+// or [0,48,16] unless `operations`).
+struct SymmPlan {
+  CellHandle cells;
+  Handle<chm_symm, chm_symm_destroy> symm;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "symmetry", "crystal");
+    check(chm_symm_create(nat.data(), (int)nat.size(), &symm.p), "chm_symm_create");
+    check(chm_cell_create(nat.data(), (int)nat.size(), &cells.p), "chm_cell_create");
   }
 };
 
@@ -568,38 +560,21 @@ std::tuple<at::Tensor, at::Tensor> symmetry(const at::Tensor& atom_types, const 
                                             const at::Tensor& lattices, std::vector<int64_t> natoms,
                                             const c10::optional<at::Tensor>& require, double symprec,
                                             double angle_tolerance, bool operations) {
-  static SymmPlans* cache = new SymmPlans;
   TORCH_CHECK(!natoms.empty(), "symmetry: natoms is empty");
   const c10::Device dev = frac.device();
-  need_on(atom_types, dev, at::kLong, "atom_types");
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  int64_t N = 0;
-  for (int64_t n : natoms) N += n;
-  const int64_t B = (int64_t)natoms.size();
-  need_shape(atom_types, {N}, "atom_types");
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
-  const int32_t* rq = nullptr;
-  int64_t n_rq = 0;
-  if (require.has_value()) {
-    need_on(*require, dev, at::kInt, "require");
-    TORCH_CHECK(require->dim() == 1 && (require->size(0) == 1 || require->size(0) == B),
-                "require: expected shape [1] or [", B, "], got ", require->sizes());
-    rq = require->data_ptr<int32_t>();
-    n_rq = require->numel();
-  }
+  const int64_t B = need_crystals(dev, natoms, &atom_types, frac, lattices).B;
+  const auto rq = optional_require(require, dev, B);
   HIPGuardMasqueradingAsCUDA guard(dev);
-  auto plan = cache->get(natoms, dev.index());
+  const auto plan = cached_plan<SymmPlan>({natoms}, dev.index());
   const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
   at::Tensor cells = at::empty({B, 128}, bytes), rec = at::empty({B, 64}, bytes);
   at::Tensor ops = at::empty({operations ? B : 0, 48, 16}, bytes);
-  check(chm_cell_run(plan.first, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, (float)symprec,
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, (float)symprec,
                      (float)angle_tolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
         "chm_cell_run");
-  check(chm_symm_run(plan.second, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+  check(chm_symm_run(plan->symm.p, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
                      atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
-                     lattices.numel(), rq, n_rq, (float)symprec, (float)angle_tolerance, rec.data_ptr(),
+                     lattices.numel(), rq.first, rq.second, (float)symprec, (float)angle_tolerance, rec.data_ptr(),
                      (size_t)rec.numel(), operations ? ops.data_ptr() : nullptr, (size_t)ops.numel(), stream()),
         "chm_symm_run");
   return {rec, ops};
@@ -607,54 +582,21 @@ std::tuple<at::Tensor, at::Tensor> symmetry(const at::Tensor& atom_types, const 
 
 // Matching against references (chm_cell_run on both lists + chm_match_run on one stream): (records uint8 [B,64] =
 // the chm_match_record of every crystal; perm int32 [N], or [0] unless `perm`). ref_of: one reference index per
-// crystal, -1 for none. Plans are cached per (natoms, ref_natoms, ref_of, device), the last 8.
-struct MatchPlans {
-  struct Entry {
-    std::vector<int64_t> natoms, ref_natoms, ref_of;
-    int device;
-    chm_cell *cells, *ref_cells;
-    chm_match* match;
-  };
-  std::mutex mu;
-  std::vector<Entry> plans;
-  static void drop(Entry& e) {
-    chm_cell_destroy(e.cells);
-    chm_cell_destroy(e.ref_cells);
-    chm_match_destroy(e.match);
-  }
-  Entry get(const std::vector<int64_t>& natoms, const std::vector<int64_t>& ref_natoms,
-            const std::vector<int64_t>& ref_of, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (e.device == device && e.natoms == natoms && e.ref_natoms == ref_natoms && e.ref_of == ref_of) return e;
-    std::vector<int32_t> nat, rnat, of;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    for (int64_t n : ref_natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match: atoms per reference must be >= 1, got ", n);
-      rnat.push_back((int32_t)n);
-    }
-    for (int64_t r : ref_of) {
-      TORCH_CHECK(r >= -1 && r < (int64_t)ref_natoms.size(), "match: ref_of entry ", r, " outside [-1, ",
-                  ref_natoms.size(), ")");
+// crystal, -1 for none. The plan's key is (natoms, ref_natoms, ref_of).
+struct MatchPlan {
+  CellHandle cells, ref_cells;
+  Handle<chm_match, chm_match_destroy> match;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "match", "crystal"), rnat = to_int32(key[1], "match", "reference");
+    std::vector<int32_t> of;
+    for (int64_t r : key[2]) {
+      TORCH_CHECK(r >= -1 && r < (int64_t)rnat.size(), "match: ref_of entry ", r, " outside [-1, ", rnat.size(), ")");
       of.push_back((int32_t)r);
     }
-    Entry e{natoms, ref_natoms, ref_of, device, nullptr, nullptr, nullptr};
-    int rc = chm_match_create(nat.data(), (int)nat.size(), rnat.data(), (int)rnat.size(), of.data(), &e.match);
-    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &e.cells);
-    if (rc == CHM_OK) rc = chm_cell_create(rnat.data(), (int)rnat.size(), &e.ref_cells);
-    if (rc != CHM_OK) {
-      drop(e);
-      check(rc, "chm_match_create");
-    }
-    if (plans.size() >= 8) {
-      drop(plans.front());
-      plans.erase(plans.begin());
-    }
-    plans.push_back(e);
-    return e;
+    int rc = chm_match_create(nat.data(), (int)nat.size(), rnat.data(), (int)rnat.size(), of.data(), &match.p);
+    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &cells.p);
+    if (rc == CHM_OK) rc = chm_cell_create(rnat.data(), (int)rnat.size(), &ref_cells.p);
+    check(rc, "chm_match_create");
   }
 };
 
@@ -664,39 +606,28 @@ std::tuple<at::Tensor, at::Tensor> match(const at::Tensor& atom_types, const at:
                                          const at::Tensor& ref_lattices, std::vector<int64_t> ref_natoms,
                                          std::vector<int64_t> ref_of, double ltol, double stol, double angle_tol,
                                          bool perm) {
-  static MatchPlans* cache = new MatchPlans;
   TORCH_CHECK(!natoms.empty(), "match: natoms is empty");
   TORCH_CHECK(!ref_natoms.empty(), "match: ref_natoms is empty");
   const c10::Device dev = frac.device();
-  need_on(atom_types, dev, at::kLong, "atom_types");
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  need_on(ref_atom_types, dev, at::kLong, "ref_atom_types");
-  need_on(ref_frac, dev, at::kFloat, "ref_frac");
-  need_on(ref_lattices, dev, at::kFloat, "ref_lattices");
-  int64_t N = 0, NR = 0;
-  for (int64_t n : natoms) N += n;
-  for (int64_t n : ref_natoms) NR += n;
-  const int64_t B = (int64_t)natoms.size(), R = (int64_t)ref_natoms.size();
-  TORCH_CHECK((int64_t)ref_of.size() == B, "ref_of: expected ", B, " entries, got ", ref_of.size());
-  need_shape(atom_types, {N}, "atom_types");
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
-  need_shape(ref_atom_types, {NR}, "ref_atom_types");
-  need_shape(ref_frac, {NR, 3}, "ref_frac");
-  need_shape(ref_lattices, {R, 3, 3}, "ref_lattices");
+  need_crystals_on(dev, &atom_types, frac, lattices);
+  need_crystals_on(dev, &ref_atom_types, ref_frac, ref_lattices, "ref_");
+  TORCH_CHECK(ref_of.size() == natoms.size(), "ref_of: expected ", natoms.size(), " entries, got ", ref_of.size());
+  const Crystals c = need_crystals_shape(natoms, &atom_types, frac, lattices);
+  const int64_t R = need_crystals_shape(ref_natoms, &ref_atom_types, ref_frac, ref_lattices, "ref_").B;
   HIPGuardMasqueradingAsCUDA guard(dev);
-  auto plan = cache->get(natoms, ref_natoms, ref_of, dev.index());
+  const auto plan = cached_plan<MatchPlan>({natoms, ref_natoms, ref_of}, dev.index());
   const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
-  at::Tensor cells = at::empty({B, 128}, bytes), ref_cells = at::empty({R, 128}, bytes), rec = at::empty({B, 64}, bytes);
-  at::Tensor pm = at::empty({perm ? N : 0}, at::TensorOptions().dtype(at::kInt).device(dev));
-  check(chm_cell_run(plan.cells, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, 0.1f, 10.0f, cells.data_ptr(),
-                     (size_t)cells.numel(), stream()),
+  at::Tensor cells = at::empty({c.B, 128}, bytes), ref_cells = at::empty({R, 128}, bytes),
+             rec = at::empty({c.B, 64}, bytes);
+  at::Tensor pm = at::empty({perm ? c.N : 0}, at::TensorOptions().dtype(at::kInt).device(dev));
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, kMatchCellSymprec,
+                     kMatchCellAngleTolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
         "chm_cell_run");
-  check(chm_cell_run(plan.ref_cells, ref_lattices.data_ptr<float>(), ref_lattices.numel(), nullptr, 0, 0.1f, 10.0f,
-                     ref_cells.data_ptr(), (size_t)ref_cells.numel(), stream()),
+  check(chm_cell_run(plan->ref_cells.p, ref_lattices.data_ptr<float>(), ref_lattices.numel(), nullptr, 0,
+                     kMatchCellSymprec, kMatchCellAngleTolerance, ref_cells.data_ptr(), (size_t)ref_cells.numel(),
+                     stream()),
         "chm_cell_run");
-  check(chm_match_run(plan.match, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+  check(chm_match_run(plan->match.p, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
                       atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
                       lattices.numel(), ref_cells.data_ptr(), (size_t)ref_cells.numel(),
                       ref_atom_types.data_ptr<int64_t>(), ref_atom_types.numel(), ref_frac.data_ptr<float>(),
@@ -709,43 +640,15 @@ std::tuple<at::Tensor, at::Tensor> match(const at::Tensor& atom_types, const at:
 
 // Grouping by pairwise matching (chm_cell_run + chm_match_group_run on one stream): (group [B] int32: the
 // representative's index or -1, count [B] int32: the group's size at a representative, records uint8 [B,32] = the
-// chm_match_group_record of every crystal, pair records uint8 [P,16] in the plan's pair order). exclude: a bool /
-// uint8 tensor [B] of crystals that take no part, or None. Plans are cached per (natoms, device), the last 8.
-struct MatchGroupPlans {
-  struct Entry {
-    std::vector<int64_t> natoms;
-    int device;
-    chm_cell* cells;
-    chm_match_group* group;
-  };
-  std::mutex mu;
-  std::vector<Entry> plans;
-  static void drop(Entry& e) {
-    chm_cell_destroy(e.cells);
-    chm_match_group_destroy(e.group);
-  }
-  Entry get(const std::vector<int64_t>& natoms, int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : plans)
-      if (e.device == device && e.natoms == natoms) return e;
-    std::vector<int32_t> nat;
-    for (int64_t n : natoms) {
-      TORCH_CHECK(n >= 1 && n <= INT32_MAX, "match_group: atoms per crystal must be >= 1, got ", n);
-      nat.push_back((int32_t)n);
-    }
-    Entry e{natoms, device, nullptr, nullptr};
-    int rc = chm_match_group_create(nat.data(), (int)nat.size(), &e.group);
-    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &e.cells);
-    if (rc != CHM_OK) {
-      drop(e);
-      check(rc, "chm_match_group_create");
-    }
-    if (plans.size() >= 8) {
-      drop(plans.front());
-      plans.erase(plans.begin());
-    }
-    plans.push_back(e);
-    return e;
+// chm_match_group_record of every crystal, pair records uint8 [P,16] in the plan's pair order).
+struct MatchGroupPlan {
+  CellHandle cells;
+  Handle<chm_match_group, chm_match_group_destroy> group;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "match_group", "crystal");
+    int rc = chm_match_group_create(nat.data(), (int)nat.size(), &group.p);
+    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &cells.p);
+    check(rc, "chm_match_group_create");
   }
 };
 
@@ -754,38 +657,22 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> match_group(const at:
                                                                        std::vector<int64_t> natoms,
                                                                        const c10::optional<at::Tensor>& exclude,
                                                                        double ltol, double stol, double angle_tol) {
-  static MatchGroupPlans* cache = new MatchGroupPlans;
   TORCH_CHECK(!natoms.empty(), "match_group: natoms is empty");
   const c10::Device dev = frac.device();
-  need_on(atom_types, dev, at::kLong, "atom_types");
-  need_on(frac, dev, at::kFloat, "frac");
-  need_on(lattices, dev, at::kFloat, "lattices");
-  int64_t N = 0;
-  for (int64_t n : natoms) N += n;
-  const int64_t B = (int64_t)natoms.size();
-  need_shape(atom_types, {N}, "atom_types");
-  need_shape(frac, {N, 3}, "frac");
-  need_shape(lattices, {B, 3, 3}, "lattices");
-  const uint8_t* ex = nullptr;
-  if (exclude.has_value()) {
-    TORCH_CHECK(exclude->scalar_type() == at::kBool || exclude->scalar_type() == at::kByte,
-                "exclude: expected bool or uint8, got ", exclude->scalar_type());
-    need_on(*exclude, dev, exclude->scalar_type(), "exclude");
-    need_shape(*exclude, {B}, "exclude");
-    ex = static_cast<const uint8_t*>(exclude->data_ptr());
-  }
+  const int64_t B = need_crystals(dev, natoms, &atom_types, frac, lattices).B;
+  const uint8_t* ex = optional_exclude(exclude, dev, B);
   HIPGuardMasqueradingAsCUDA guard(dev);
-  auto plan = cache->get(natoms, dev.index());
-  const int64_t P = chm_match_group_num_pairs(plan.group);
-  const size_t ws_bytes = chm_match_group_workspace_bytes(plan.group);
+  const auto plan = cached_plan<MatchGroupPlan>({natoms}, dev.index());
+  const int64_t P = chm_match_group_num_pairs(plan->group.p);
+  const size_t ws_bytes = chm_match_group_workspace_bytes(plan->group.p);
   const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
   const auto ints = at::TensorOptions().dtype(at::kInt).device(dev);
   at::Tensor cells = at::empty({B, 128}, bytes), rec = at::empty({B, 32}, bytes), pairs = at::empty({P, 16}, bytes),
              ws = at::empty({(int64_t)ws_bytes}, bytes), group = at::empty({B}, ints), count = at::empty({B}, ints);
-  check(chm_cell_run(plan.cells, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, 0.1f, 10.0f, cells.data_ptr(),
-                     (size_t)cells.numel(), stream()),
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, kMatchCellSymprec,
+                     kMatchCellAngleTolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
         "chm_cell_run");
-  check(chm_match_group_run(plan.group, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+  check(chm_match_group_run(plan->group.p, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
                             atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
                             lattices.numel(), ex, ex ? B : 0, (float)ltol, (float)stol, (float)angle_tol,
                             group.data_ptr<int32_t>(), group.numel(), count.data_ptr<int32_t>(), count.numel(),

@@ -19,16 +19,14 @@ change of lattice basis and choice of supercell) differ by at most `tol` relativ
 criterion agrees with the matcher has not been measured ("Grouping duplicates").
 """
 
-import ctypes
 import math
-import threading
-from collections import OrderedDict
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from chemeleon_amd import _lib
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state, exclude_tensor
 
 DEGENERATE, NONFINITE = 8, 16
 CLASSES = 104
@@ -90,17 +88,10 @@ class DedupReport:
         return {"index": int(g), "group": int(self.group[g]), "multiplicity": int(self.count[g])}
 
 
-class DedupPlan:
+class DedupPlan(Plan):
     """Owns a chm_dedup: the node offsets of one crystal list on one device."""
 
-    def __init__(self, natoms: Sequence[int], device):
-        self.natoms = tuple(int(n) for n in natoms)
-        self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().chm_dedup_create(nat, len(self.natoms), ctypes.byref(h)), "chm_dedup_create")
-        self.handle = h
+    _create, _destroy = "chm_dedup_create", "chm_dedup_destroy"
 
     def fingerprint(self, atom_types, frac_coords, lattices, dedup: Dedup, fp, counts, flags):
         """Enqueues the fingerprint kernel on the current stream of the plan's device. No host wait."""
@@ -110,33 +101,13 @@ class DedupPlan:
             _lib.ptr(counts), counts.numel(), _lib.ptr(flags), flags.numel(), _lib.stream_handle(self.device)),
             "chm_dedup_fingerprint")
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_dedup_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, DedupPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(DedupPlan)
 
 
 def dedup_plan(natoms: Sequence[int], device) -> DedupPlan:
     """The plan of this crystal list on this device, cached per (natoms, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = DedupPlan(key[0], dev)
-        return p
+    return _plans.get(device, natoms)
 
 
 def _need_dedup(dedup) -> Dedup:
@@ -153,18 +124,8 @@ def fingerprint_states(natoms: Sequence[int], atom_types, frac_coords, lattices,
     lattices [B,3,3] fp32, in node order of `natoms`), left on the device. CPU tensors are refused: there is no
     host path. No host wait."""
     dedup = _need_dedup(dedup)
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    N, B = sum(nat), len(nat)
-    if tuple(atom_types.shape) != (N,) or tuple(frac_coords.shape) != (N, 3) or tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if atom_types.dtype != torch.int64 or frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be atom_types int64, frac_coords / lattices float32")
-    dev = frac_coords.device
-    if atom_types.device != dev or lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
+    nat = check_natoms(natoms)
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices)
     plan = dedup_plan(nat, dev)
     with torch.cuda.device(dev):
         fp = torch.empty(B, 2 * dedup.bins, dtype=torch.float32, device=dev)
@@ -214,13 +175,7 @@ def group_fingerprints(fps: Union[Fingerprints, Sequence[Fingerprints]], dedup: 
     B = sum(len(f) for f in many)
     if B < 1:
         raise ValueError("no fingerprints to group")
-    ex = None
-    if exclude is not None:
-        ex = exclude if torch.is_tensor(exclude) else torch.from_numpy(np.ascontiguousarray(np.asarray(exclude)))
-        if tuple(ex.shape) != (B,):
-            raise ValueError(f"exclude has shape {tuple(ex.shape)}, the fingerprints list {B} crystals")
-        if ex.dtype not in (torch.bool, torch.uint8):
-            raise ValueError("exclude must be bool or uint8")
+    ex = exclude_tensor(exclude, B, "the fingerprints list")
     for f in many:
         _lib.require_device(f.fp, f.counts, f.flags)
     dev = many[0].fp.device

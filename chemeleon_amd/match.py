@@ -25,9 +25,7 @@ reference; the pairing is the nearest-partner rule, not an optimal assignment (D
 reference").
 """
 
-import ctypes
 import threading
-from collections import OrderedDict
 from typing import Optional, Sequence
 
 import numpy as np
@@ -35,6 +33,7 @@ import torch
 
 from chemeleon_amd import _lib
 from chemeleon_amd import cell as _cell
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state, hip_device, int32_array
 
 NO_REFERENCE, NO_LATTICE, SIZE, COMPOSITION, THIN, MANY_MAPPINGS = 1, 2, 4, 8, 16, 32
 FLAG_NAMES = {NO_REFERENCE: "no_reference", NO_LATTICE: "no_lattice", SIZE: "size", COMPOSITION: "composition",
@@ -43,6 +42,8 @@ RECORD_BYTES = 64
 MAX_ATOMS = 256
 MAX_MAPPINGS = 256
 MAX_LTOL, MAX_STOL, MAX_ANGLE_TOL = 1.0, 1.0, 30.0
+# the tolerances of the cell pass whose records the matcher reads (both lists, every caller)
+MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE = 0.1, 10.0
 
 
 class Reference:
@@ -92,11 +93,7 @@ class Reference:
 
     def on(self, device):
         """(atom_types, frac_coords, lattices, cell records) on `device`, made once per device."""
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = hip_device(device)
         with self._lock:
             held = self._on.get(dev.index)
             if held is None:
@@ -105,7 +102,7 @@ class Reference:
                     x = torch.from_numpy(self.frac_coords).to(dev)
                     lat = torch.from_numpy(self.lattices).to(dev)
                     rec = torch.empty(len(self.natoms) * _cell.RECORD_BYTES, dtype=torch.uint8, device=dev)
-                    _cell.cell_plan(self.natoms, dev).run(lat, None, 0.1, 10.0, rec)
+                    _cell.cell_plan(self.natoms, dev).run(lat, None, MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE, rec)
                     torch.cuda.current_stream(dev).synchronize()
                 held = self._on[dev.index] = (a, x, lat, rec)
             return held
@@ -201,23 +198,19 @@ class MatchReport:
                 "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit], "ref": int(self.ref[g])}
 
 
-class MatchPlan:
+class MatchPlan(Plan):
     """Owns a chm_match: the node offsets of a crystal list and a reference list, and ref_of, on one device."""
+
+    _create, _destroy = "chm_match_create", "chm_match_destroy"
 
     def __init__(self, natoms: Sequence[int], ref_natoms: Sequence[int], ref_of: Sequence[int], device):
         self.natoms, self.ref_natoms = tuple(int(n) for n in natoms), tuple(int(n) for n in ref_natoms)
         self.ref_of = tuple(int(r) for r in ref_of)
         self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        rnat = (ctypes.c_int32 * len(self.ref_natoms))(*self.ref_natoms)
-        of = (ctypes.c_int32 * len(self.ref_of))(*self.ref_of)
         if len(self.ref_of) != len(self.natoms):
             raise ValueError(f"ref_of lists {len(self.ref_of)} crystals, natoms {len(self.natoms)}")
-        h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().chm_match_create(nat, len(self.natoms), rnat, len(self.ref_natoms), of,
-                                                    ctypes.byref(h)), "chm_match_create")
-        self.handle = h
+        self._make(int32_array(self.natoms), len(self.natoms), int32_array(self.ref_natoms), len(self.ref_natoms),
+                   int32_array(self.ref_of))
 
     def run(self, cell_records, atom_types, frac_coords, lattices, ref_cell_records, ref_atom_types, ref_frac_coords,
             ref_lattices, ltol: float, stol: float, angle_tol: float, out, perm=None):
@@ -233,33 +226,13 @@ class MatchPlan:
             0 if perm is None else perm.numel(), _lib.stream_handle(self.device)), "chm_match_run")
         return out
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_match_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, MatchPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(MatchPlan)
 
 
 def match_plan(natoms: Sequence[int], ref_natoms: Sequence[int], ref_of: Sequence[int], device) -> MatchPlan:
     """The plan of these lists on this device, cached per (natoms, ref_natoms, ref_of, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), tuple(int(n) for n in ref_natoms), tuple(int(r) for r in ref_of), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = MatchPlan(key[0], key[1], key[2], dev)
-        return p
+    return _plans.get(device, natoms, ref_natoms, ref_of)
 
 
 def match_states(natoms: Sequence[int], atom_types, frac_coords, lattices, match: Match, perm: bool = False) -> MatchReport:
@@ -269,28 +242,16 @@ def match_states(natoms: Sequence[int], atom_types, frac_coords, lattices, match
     asked for) cross to the host. CPU tensors are refused: there is no host path."""
     if not isinstance(match, Match):
         raise ValueError("match must be a chemeleon_amd.Match")
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    if max(nat) > MAX_ATOMS:
-        raise ValueError(f"the matcher holds at most {MAX_ATOMS} atoms per crystal, got {max(nat)}")
-    N, B = sum(nat), len(nat)
-    ref_of = match.ref_of_for(B)
-    if tuple(atom_types.shape) != (N,) or tuple(frac_coords.shape) != (N, 3) or tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if atom_types.dtype != torch.int64 or frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be atom_types int64, frac_coords / lattices float32")
-    dev = frac_coords.device
-    if atom_types.device != dev or lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
+    nat = check_natoms(natoms, MAX_ATOMS, "the matcher")
+    ref_of = match.ref_of_for(len(nat))
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices)
     ra, rx, rlat, rrec = match.reference.on(dev)
     cells, plan = _cell.cell_plan(nat, dev), match_plan(nat, match.reference.natoms, ref_of, dev)
     with torch.cuda.device(dev):
         cell_rec = torch.empty(B * _cell.RECORD_BYTES, dtype=torch.uint8, device=dev)
         out = torch.empty(B * RECORD_BYTES, dtype=torch.uint8, device=dev)
         pm = torch.empty(N, dtype=torch.int32, device=dev) if perm else None
-        cells.run(lattices, None, 0.1, 10.0, cell_rec)
+        cells.run(lattices, None, MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE, cell_rec)
         plan.run(cell_rec, atom_types, frac_coords, lattices, rrec, ra, rx, rlat, match.ltol, match.stol,
                  match.angle_tol, out, pm)
         host = out.cpu().numpy()  # (waits for the kernels; cell_rec and out stay alive until here)

@@ -23,9 +23,6 @@ primitive cell; the pairing is the nearest-partner rule, not an optimal assignme
 duplicates by matching").
 """
 
-import ctypes
-import threading
-from collections import OrderedDict
 from typing import Optional, Sequence
 
 import numpy as np
@@ -33,8 +30,9 @@ import torch
 
 from chemeleon_amd import _lib
 from chemeleon_amd import cell as _cell
-from chemeleon_amd.match import (COMPOSITION, MANY_MAPPINGS, MAX_ANGLE_TOL, MAX_ATOMS, MAX_LTOL, MAX_STOL, NO_LATTICE,
-                                 THIN)
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state, exclude_tensor
+from chemeleon_amd.match import (COMPOSITION, MANY_MAPPINGS, MATCH_CELL_ANGLE_TOLERANCE, MATCH_CELL_SYMPREC, MAX_ANGLE_TOL,
+                                 MAX_ATOMS, MAX_LTOL, MAX_STOL, NO_LATTICE, THIN)
 
 EXCLUDED = 64
 FLAG_NAMES = {NO_LATTICE: "no_lattice", COMPOSITION: "composition", THIN: "thin", MANY_MAPPINGS: "many_mappings",
@@ -108,20 +106,16 @@ class MatchGroupReport:
                 "rms": float(self.rms[g])}
 
 
-class MatchGroupPlan:
+class MatchGroupPlan(Plan):
     """Owns a chm_match_group: the node offsets and the pair table of one crystal list on one device."""
 
+    _create, _destroy = "chm_match_group_create", "chm_match_group_destroy"
+
     def __init__(self, natoms: Sequence[int], device):
-        self.natoms = tuple(int(n) for n in natoms)
-        self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        h = _lib.c_void_p()
+        super().__init__(natoms, device)
         lib = _lib.load()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.chm_match_group_create(nat, len(self.natoms), ctypes.byref(h)), "chm_match_group_create")
-        self.handle = h
-        self.num_pairs = int(lib.chm_match_group_num_pairs(h))
-        self.workspace_bytes = int(lib.chm_match_group_workspace_bytes(h))
+        self.num_pairs = int(lib.chm_match_group_num_pairs(self.handle))
+        self.workspace_bytes = int(lib.chm_match_group_workspace_bytes(self.handle))
 
     def run(self, cell_records, atom_types, frac_coords, lattices, exclude, ltol: float, stol: float, angle_tol: float,
             group, count, out, pair_records, workspace):
@@ -137,33 +131,13 @@ class MatchGroupPlan:
             pair_records.numel(), _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)),
             "chm_match_group_run")
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_match_group_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, MatchGroupPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(MatchGroupPlan)
 
 
 def match_group_plan(natoms: Sequence[int], device) -> MatchGroupPlan:
     """The plan of this crystal list on this device, cached per (natoms, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = MatchGroupPlan(key[0], dev)
-        return p
+    return _plans.get(device, natoms)
 
 
 def _need_dedup(dedup) -> MatchDedup:
@@ -182,27 +156,9 @@ def match_group_states(natoms: Sequence[int], atom_types, frac_coords, lattices,
     records cross to the host. `exclude` (a bool / 0-1 array or tensor [B]) marks crystals that take no part: they
     get group -1. CPU tensors are refused: there is no host path."""
     dedup = _need_dedup(dedup)
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    if max(nat) > MAX_ATOMS:
-        raise ValueError(f"the matcher holds at most {MAX_ATOMS} atoms per crystal, got {max(nat)}")
-    N, B = sum(nat), len(nat)
-    if tuple(atom_types.shape) != (N,) or tuple(frac_coords.shape) != (N, 3) or tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if atom_types.dtype != torch.int64 or frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be atom_types int64, frac_coords / lattices float32")
-    dev = frac_coords.device
-    if atom_types.device != dev or lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
-    ex = None
-    if exclude is not None:
-        ex = exclude if torch.is_tensor(exclude) else torch.from_numpy(np.ascontiguousarray(np.asarray(exclude)))
-        if tuple(ex.shape) != (B,):
-            raise ValueError(f"exclude has shape {tuple(ex.shape)}, the state lists {B} crystals")
-        if ex.dtype not in (torch.bool, torch.uint8):
-            raise ValueError("exclude must be bool or uint8")
+    nat = check_natoms(natoms, MAX_ATOMS, "the matcher")
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices)
+    ex = exclude_tensor(exclude, B, "the state lists")
     cells, plan = _cell.cell_plan(nat, dev), match_group_plan(nat, dev)
     with torch.cuda.device(dev):
         if ex is not None:
@@ -212,7 +168,7 @@ def match_group_states(natoms: Sequence[int], atom_types, frac_coords, lattices,
         out = torch.empty(B * RECORD_BYTES, dtype=torch.uint8, device=dev)
         pair_rec = torch.empty(plan.num_pairs * PAIR_RECORD_BYTES, dtype=torch.uint8, device=dev)
         ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=dev)
-        cells.run(lattices, None, 0.1, 10.0, cell_rec)
+        cells.run(lattices, None, MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE, cell_rec)
         plan.run(cell_rec, atom_types, frac_coords, lattices, ex, dedup.ltol, dedup.stol, dedup.angle_tol, group[0],
                  group[1], out, pair_rec, ws)
         host = group.cpu().numpy()  # (waits for the kernels; every buffer stays alive until here)

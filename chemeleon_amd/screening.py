@@ -16,16 +16,14 @@ One deliberate difference from the reference's filter: its `np.min(dist_mat[dist
 coincident atoms; here they give dmin = 0 and fail the screen.
 """
 
-import ctypes
 import math
-import threading
-from collections import OrderedDict
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from chemeleon_amd import _lib
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state
 from chemeleon_amd.constraints import MAX_ATOMS, parse_formula
 
 TOO_LONG, TOO_CLOSE, COMPOSITION, DEGENERATE, NONFINITE = 1, 2, 4, 8, 16
@@ -113,17 +111,10 @@ class ScreenReport:
                 "flags": fl, "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit], "valid": fl == 0}
 
 
-class ScreenPlan:
+class ScreenPlan(Plan):
     """Owns a chm_screen: the node offsets of one crystal list on one device."""
 
-    def __init__(self, natoms: Sequence[int], device):
-        self.natoms = tuple(int(n) for n in natoms)
-        self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().chm_screen_create(nat, len(self.natoms), ctypes.byref(h)), "chm_screen_create")
-        self.handle = h
+    _create, _destroy = "chm_screen_create", "chm_screen_destroy"
 
     def run(self, atom_types, frac_coords, lattices, target, max_length: float, min_distance: float, out):
         """Enqueues the screen on the current stream of the plan's device; `out` is a uint8 device tensor of 64
@@ -135,33 +126,13 @@ class ScreenPlan:
             "chm_screen_run")
         return out
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_screen_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, ScreenPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(ScreenPlan)
 
 
 def screen_plan(natoms: Sequence[int], device) -> ScreenPlan:
     """The plan of this crystal list on this device, cached per (natoms, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = ScreenPlan(key[0], dev)
-        return p
+    return _plans.get(device, natoms)
 
 
 def screen_states(natoms: Sequence[int], atom_types, frac_coords, lattices, screen: Optional[Screen] = None
@@ -170,19 +141,9 @@ def screen_states(natoms: Sequence[int], atom_types, frac_coords, lattices, scre
     fp32, in node order of `natoms`) and returns its ScreenReport; only the 64-byte records cross to the host.
     CPU tensors are refused: there is no host path."""
     screen = Screen() if screen is None else screen
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    N, B = sum(nat), len(nat)
-    target = screen.target_for(B)
-    if tuple(atom_types.shape) != (N,) or tuple(frac_coords.shape) != (N, 3) or tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if atom_types.dtype != torch.int64 or frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be atom_types int64, frac_coords / lattices float32")
-    dev = frac_coords.device
-    if atom_types.device != dev or lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
+    nat = check_natoms(natoms)
+    target = screen.target_for(len(nat))
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices)
     plan = screen_plan(nat, dev)
     with torch.cuda.device(dev):
         tg = None if target is None else torch.from_numpy(np.ascontiguousarray(target)).to(dev)

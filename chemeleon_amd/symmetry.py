@@ -23,9 +23,6 @@ lattice has lower symmetry than the primitive lattice (a 2x1x1 cell of CsCl) rep
 space-group number and the point group's name are not built ("Crystal system with the atoms").
 """
 
-import ctypes
-import threading
-from collections import OrderedDict
 from typing import Optional, Sequence, Union
 
 import numpy as np
@@ -33,6 +30,7 @@ import torch
 
 from chemeleon_amd import _lib
 from chemeleon_amd import cell as _cell
+from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state
 
 CRYSTAL_SYSTEMS = ("triclinic", "monoclinic", "orthorhombic", "tetragonal", "trigonal", "hexagonal", "cubic")
 AMBIGUOUS, MISMATCH, NO_LATTICE, THIN = 1, 2, 4, 8
@@ -155,17 +153,10 @@ class SymmetryReport:
                 "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit], "valid": bool(self.valid[g])}
 
 
-class SymmetryPlan:
+class SymmetryPlan(Plan):
     """Owns a chm_symm: the node offsets of one crystal list on one device."""
 
-    def __init__(self, natoms: Sequence[int], device):
-        self.natoms = tuple(int(n) for n in natoms)
-        self.device = torch.device(device)
-        nat = (ctypes.c_int32 * len(self.natoms))(*self.natoms)
-        h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().chm_symm_create(nat, len(self.natoms), ctypes.byref(h)), "chm_symm_create")
-        self.handle = h
+    _create, _destroy = "chm_symm_create", "chm_symm_destroy"
 
     def run(self, cell_records, atom_types, frac_coords, lattices, require, symprec: float, angle_tolerance: float,
             out, ops=None):
@@ -180,33 +171,13 @@ class SymmetryPlan:
             "chm_symm_run")
         return out
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().chm_symm_destroy(self.handle)
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
 
-
-_plans: "OrderedDict[tuple, SymmetryPlan]" = OrderedDict()
-_plans_lock = threading.Lock()
+_plans = PlanCache(SymmetryPlan)
 
 
 def symmetry_plan(natoms: Sequence[int], device) -> SymmetryPlan:
     """The plan of this crystal list on this device, cached per (natoms, device) (the last 8)."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("chemeleon_amd runs on a HIP device only: got " + str(dev))
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (tuple(int(n) for n in natoms), dev.index)
-    with _plans_lock:
-        p = _plans.get(key)
-        if p is None:
-            if len(_plans) >= 8:
-                _plans.popitem(last=False)
-            p = _plans[key] = SymmetryPlan(key[0], dev)
-        return p
+    return _plans.get(device, natoms)
 
 
 def symmetry_states(natoms: Sequence[int], atom_types, frac_coords, lattices, symmetry: Optional[Symmetry] = None,
@@ -219,19 +190,9 @@ def symmetry_states(natoms: Sequence[int], atom_types, frac_coords, lattices, sy
         symmetry = Symmetry()
     if not isinstance(symmetry, Symmetry):
         raise ValueError("symmetry must be a chemeleon_amd.Symmetry")
-    nat = [int(n) for n in natoms]
-    if not nat or min(nat) < 1:
-        raise ValueError("natoms must list at least one crystal of at least one atom")
-    N, B = sum(nat), len(nat)
-    codes = symmetry.codes_for(B)
-    if tuple(atom_types.shape) != (N,) or tuple(frac_coords.shape) != (N, 3) or tuple(lattices.shape) != (B, 3, 3):
-        raise ValueError("state shapes do not match natoms")
-    _lib.require_device(atom_types, frac_coords, lattices)
-    if atom_types.dtype != torch.int64 or frac_coords.dtype != torch.float32 or lattices.dtype != torch.float32:
-        raise ValueError("the state must be atom_types int64, frac_coords / lattices float32")
-    dev = frac_coords.device
-    if atom_types.device != dev or lattices.device != dev:
-        raise ValueError("the state's tensors are on different devices")
+    nat = check_natoms(natoms)
+    codes = symmetry.codes_for(len(nat))
+    N, B, dev = check_state(nat, atom_types, frac_coords, lattices)
     cells, plan = _cell.cell_plan(nat, dev), symmetry_plan(nat, dev)
     with torch.cuda.device(dev):
         rq = None if codes is None else torch.from_numpy(np.ascontiguousarray(codes)).to(dev)
