@@ -229,6 +229,11 @@ SIGNATURES = {
     "chm_symm_run": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                              c_void_p, c_i64, c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
                              c_void_p]),
+    "chm_prim_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(c_void_p)]),
+    "chm_prim_destroy": (None, [c_void_p]),
+    "chm_prim_run": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                             c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                             c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "chm_match_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(ctypes.c_int32), c_int,
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_void_p)]),
     "chm_match_destroy": (None, [c_void_p]),

@@ -20,7 +20,7 @@ DEFS = os.environ.get("CHM_BUILD_DEFS", "").split()
 if os.environ.get("CHM_BUILD_LIB"):
     LIB = os.path.abspath(os.environ["CHM_BUILD_LIB"])
     LIBDIR = os.path.dirname(LIB)
-SOURCES = ["kernels.hip", "gemm_bf16x3.hip", "split16.hip", "edge16.hip", "node_gemm.hip", "knn.hip", "snapshot.hip", "constrain.hip", "screen.hip", "dedup.hip", "cell.hip", "symm.hip", "match.hip",
+SOURCES = ["kernels.hip", "gemm_bf16x3.hip", "split16.hip", "edge16.hip", "node_gemm.hip", "knn.hip", "snapshot.hip", "constrain.hip", "screen.hip", "dedup.hip", "cell.hip", "symm.hip", "prim.hip", "match.hip",
            "model.hip", "batch.hip", "decoder.hip", "step.hip", "debug_hooks.hip", "host_noise.cpp"]
 ARCH = os.environ.get("CHM_OFFLOAD_ARCH", "gfx950")
 

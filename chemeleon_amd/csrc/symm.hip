@@ -22,6 +22,7 @@
 #include "chm_host.h"
 #include "plan_common.h"
 #include "cell_shared.h"
+#include "symm_shared.h"
 
 // Every product and sum is rounded on its own (as in cell.hip).
 #pragma clang fp contract(off)
@@ -29,6 +30,8 @@
 namespace {
 
 using namespace chm_cellshared;
+using chm_symmshared::Atom;
+using chm_symmshared::lands_on;
 
 constexpr int kBlock = 256;     // four waves per crystal
 constexpr int kMaxAtoms = 256;  // the LDS staging
@@ -47,11 +50,6 @@ struct SymmArgs {
   float symprec, angle_tolerance;
   chm_symm_record* out;
   int4* ops;  // NULL, or [B, 48] slots of (candidate index, t0, t1, t2)
-};
-
-struct __align__(16) Atom {
-  float x[3];  // in the reduced basis, [0, 1)
-  int type;
 };
 
 // (m, m2, m3, m4, m6) of the distinct proper parts -> the crystal system code, or -1
@@ -205,15 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_symm(SymmArgs p) {
           for (int q = 0; q < n && !found; ++q) {
             const Atom b = s_at[q];
             if (b.type != a.type) continue;
-            float d[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              d[k] = y[k] - b.x[k];
-              d[k] -= rintf(d[k]);
-            }
-            const float e0 = (d[0] * L[0] + d[1] * L[3]) + d[2] * L[6], e1 = (d[0] * L[1] + d[1] * L[4]) + d[2] * L[7],
-                        e2 = (d[0] * L[2] + d[1] * L[5]) + d[2] * L[8];
-            found = (e0 * e0 + e1 * e1) + e2 * e2 <= tol2;
+            found = lands_on(y, b.x, L, tol2);  // (symm_shared.h: the test k_prim runs too)
           }
           ok = found;
         }

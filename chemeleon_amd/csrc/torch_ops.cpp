@@ -330,7 +330,7 @@ at::Tensor d3pm_sample(const at::Tensor& logits, const at::Tensor& xt, const at:
 }
 
 // ---------------------------------------------------------------- finishing legs
-// screen, dedup, cell, symmetry, match and match_group share what stands between here and the first of them:
+// screen, dedup, cell, symmetry, primitive, match and match_group share what stands between here and the first of them:
 // the checks of a state against its crystal list, the optional exclude / require tensors, and one plan cache.
 // A cache keeps the plans of the last 8 (crystal lists, device) keys, evicts the oldest first and lives as long
 // as the process (nothing is freed during static destruction, when the HIP runtime may be gone). It hands out
@@ -580,6 +580,46 @@ std::tuple<at::Tensor, at::Tensor> symmetry(const at::Tensor& atom_types, const 
   return {rec, ops};
 }
 
+// Primitive cells (chm_cell_run + chm_prim_run on one stream): (atom_types int64 [N] and frac [N,3], the packed
+// primitive cells in their first new_offsets[B] rows and zero after them; lattices [B,3,3]; new_offsets int32
+// [B+1]; records uint8 [B,64] = the chm_prim_record of every crystal). Nothing crosses to the host here: the caller
+// reads N' from new_offsets.
+struct PrimPlan {
+  CellHandle cells;
+  Handle<chm_prim, chm_prim_destroy> prim;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "primitive", "crystal");
+    check(chm_prim_create(nat.data(), (int)nat.size(), &prim.p), "chm_prim_create");
+    check(chm_cell_create(nat.data(), (int)nat.size(), &cells.p), "chm_cell_create");
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> primitive(
+    const at::Tensor& atom_types, const at::Tensor& frac, const at::Tensor& lattices, std::vector<int64_t> natoms,
+    double symprec, double angle_tolerance) {
+  TORCH_CHECK(!natoms.empty(), "primitive: natoms is empty");
+  const c10::Device dev = frac.device();
+  const Crystals c = need_crystals(dev, natoms, &atom_types, frac, lattices);
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  const auto plan = cached_plan<PrimPlan>({natoms}, dev.index());
+  const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+  const auto ints = at::TensorOptions().dtype(at::kInt).device(dev);
+  at::Tensor cells = at::empty({c.B, 128}, bytes), rec = at::empty({c.B, 64}, bytes);
+  at::Tensor source = at::empty({c.N}, ints), new_off = at::empty({c.B + 1}, ints);
+  at::Tensor a_out = at::empty_like(atom_types), x_out = at::empty_like(frac), lat_out = at::empty_like(lattices);
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, (float)symprec,
+                     (float)angle_tolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_prim_run(plan->prim.p, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+                     atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
+                     lattices.numel(), (float)symprec, (float)angle_tolerance, rec.data_ptr(), (size_t)rec.numel(),
+                     source.data_ptr<int32_t>(), source.numel(), new_off.data_ptr<int32_t>(), new_off.numel(),
+                     a_out.data_ptr<int64_t>(), a_out.numel(), x_out.data_ptr<float>(), x_out.numel(),
+                     lat_out.data_ptr<float>(), lat_out.numel(), stream()),
+        "chm_prim_run");
+  return {a_out, x_out, lat_out, new_off, rec};
+}
+
 // Matching against references (chm_cell_run on both lists + chm_match_run on one stream): (records uint8 [B,64] =
 // the chm_match_record of every crystal; perm int32 [N], or [0] unless `perm`). ref_of: one reference index per
 // crystal, -1 for none. The plan's key is (natoms, ref_natoms, ref_of).
@@ -714,6 +754,8 @@ TORCH_LIBRARY(chemeleon, m) {
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("symmetry(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? require, float symprec, "
         "float angle_tolerance, bool operations) -> (Tensor, Tensor)");
+  m.def("primitive(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, float symprec, "
+        "float angle_tolerance) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("match(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor ref_atom_types, Tensor ref_frac, "
         "Tensor ref_lattices, int[] ref_natoms, int[] ref_of, float ltol, float stol, float angle_tol, bool perm) -> "
         "(Tensor, Tensor)");
@@ -730,6 +772,7 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("dedup", dedup);
   m.impl("cell", cell);
   m.impl("symmetry", symmetry);
+  m.impl("primitive", primitive);
   m.impl("match", match);
   m.impl("match_group", match_group);
 }

@@ -1,5 +1,5 @@
 """The tail of Chemeleon.sample(): the optional legs that run on the finished state on the device (the screen,
-chemeleon_amd.screening; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the matching,
+chemeleon_amd.screening; the primitive cell, chemeleon_amd.primitive; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the matching,
 chemeleon_amd.match; the grouping, chemeleon_amd.dedup or, with a MatchDedup, chemeleon_amd.match_group), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
 
 from typing import Sequence
@@ -8,21 +8,26 @@ import numpy as np
 
 
 def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen=None, cell=None, symmetry=None,
-                 dedup=None, match=None):
-    """(structures, reports): the tail of sample() with any of its five optional legs, in this order: the screen,
+                 dedup=None, match=None, primitive=None):
+    """(structures, reports): the tail of sample() with any of its optional legs, in this order: the screen,
+    the primitive cell (which replaces the state for every leg after it and for the structures returned),
     the cell, the symmetry, the matching, then the grouping, from which the failures of the first four (a screen
     flag; a required lattice system or crystal system not met; with match.require, no match) are excluded. Only the structures that pass (with dedup:
     one representative per group) are copied and converted (in their reduced cells with cell.reduce), each with
-    atoms.info["screen"] / ["cell"] / ["symmetry"] / ["match"] / ["dedup"] for the legs that ran. `reports` is a
-    dict with the report of each leg that ran under the same five names."""
+    atoms.info["screen"] / ["primitive"] / ["cell"] / ["symmetry"] / ["match"] / ["dedup"] for the legs that ran.
+    `reports` is a dict with the report of each leg that ran under the same names."""
     from chemeleon_amd.screening import screen_states, selected_atoms
     nat = [int(n) for n in natoms]
     reports = {}
     failed = None
-    x, lat = frac_coords, lattices
     if screen is not None:
         reports["screen"] = screen_states(nat, atom_types, frac_coords, lattices, screen)
         failed = ~reports["screen"].valid
+    if primitive is not None:  # (from here on the state is the primitive cells': the crystals keep their indices)
+        from chemeleon_amd.primitive import primitive_states
+        nat, atom_types, frac_coords, lattices, reports["primitive"] = primitive_states(
+            nat, atom_types, frac_coords, lattices, primitive)
+    x, lat = frac_coords, lattices
     if cell is not None:
         from chemeleon_amd.cell import _run
         x_r, lat_r, reports["cell"] = _run(nat, atom_types, frac_coords, lattices, cell, cell.reduce)
@@ -56,6 +61,8 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
     for at, g in zip(atoms, keep):
         if "screen" in reports:
             at.info["screen"] = dict(reports["screen"].record(g), index=g)
+        if "primitive" in reports:
+            at.info["primitive"] = dict(reports["primitive"].record(g), index=g)
         if "cell" in reports:
             at.info["cell"] = dict(reports["cell"].record(g), index=g, reduced=cell.reduce)
         if "symmetry" in reports:

@@ -21,8 +21,8 @@ the smallest rms displacement (mean removed, in units of l) is the answer. The d
 
 This is not a port of pymatgen, and how far the two agree (StructureMatcher.fit) has not been measured. Atom
 counts must be equal: there is no reduction to a primitive cell, so a supercell does not match its primitive
-reference; the pairing is the nearest-partner rule, not an optimal assignment ("Matching a
-reference").
+reference (chemeleon_amd.primitive, primitive_states or sample(primitive=...), is the way round it: it runs first);
+the pairing is the nearest-partner rule, not an optimal assignment ("Matching a reference").
 """
 
 import threading

@@ -19,8 +19,9 @@ one it matches (the rule of chemeleon_amd.dedup; not transitive).
 
 This is not a port of StructureMatcher, and how far the groups agree with group_structures has not been measured.
 Atom counts must be equal: there is no reduction to a primitive cell, so a supercell is never grouped with its
-primitive cell; the pairing is the nearest-partner rule, not an optimal assignment ("Grouping
-duplicates by matching").
+primitive cell (chemeleon_amd.primitive, primitive_states or sample(primitive=...), is the way round it: it runs
+first); the pairing is the nearest-partner rule, not an optimal assignment ("Grouping duplicates by
+matching").
 """
 
 from typing import Optional, Sequence

@@ -60,6 +60,7 @@ class Chemeleon(nn.Module):
     last_dedup = None   # the DedupReport of the last sample(..., dedup=...) call
     last_cell = None    # the CellReport of the last sample(..., cell=...) call
     last_symmetry = None  # the SymmetryReport of the last sample(..., symmetry=...) call
+    last_primitive = None  # the PrimitiveReport of the last sample(..., primitive=...) call
     last_match = None  # the MatchReport of the last sample(..., match=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
@@ -652,7 +653,7 @@ class Chemeleon(nn.Module):
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
                group=None, overlap: bool = True, screen=None, dedup=None, cell=None, symmetry=None,
-               match=None, **kw):
+               match=None, primitive=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -712,8 +713,26 @@ class Chemeleon(nn.Module):
         self.last_match (match_rate, rms_mean). With require=True only the structures that match are returned,
         and the others take no part in the grouping. Like the screen it is for finished structures (ValueError
         with stream / return_trajectory) and runs on the gathered final state on every rank, with no collective
-        of its own. Without the keyword nothing of it runs."""
+        of its own. Without the keyword nothing of it runs.
+
+        primitive=Primitive(...) (chemeleon_amd.primitive): every finished structure is reduced to a primitive
+        cell on the device, after the screen and before every other leg: the cell, the symmetry, the matching and
+        the grouping then see the primitive cells, and the structures returned are the primitive cells, each with
+        atoms.info["primitive"]; the whole report is kept as self.last_primitive. A structure without
+        translations comes back as it is, in its Niggli-reduced basis. Like the screen it is for finished
+        structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
+        rank. Without the keyword nothing of it runs."""
         natoms = [n_atoms] * n_samples
+        if primitive is not None:
+            from chemeleon_amd.primitive import MAX_ATOMS as PRIMITIVE_MAX_ATOMS
+            from chemeleon_amd.primitive import Primitive
+            if not isinstance(primitive, Primitive):
+                raise ValueError("primitive must be a chemeleon_amd.Primitive")
+            if stream or return_trajectory:
+                raise ValueError("primitive= applies to finished structures: not with stream / return_trajectory")
+            if n_atoms > PRIMITIVE_MAX_ATOMS:
+                raise ValueError(f"primitive= holds at most {PRIMITIVE_MAX_ATOMS} atoms per crystal, got "
+                                 f"n_atoms={n_atoms}")
         if match is not None:
             from chemeleon_amd.match import MAX_ATOMS as MATCH_MAX_ATOMS
             from chemeleon_amd.match import Match
@@ -775,10 +794,11 @@ class Chemeleon(nn.Module):
         for last in it:
             pass
         _, a, x, lat = last
-        if screen is not None or cell is not None or symmetry is not None or dedup is not None or match is not None:
+        if screen is not None or cell is not None or symmetry is not None or dedup is not None or match is not None \
+                or primitive is not None:
             from chemeleon_amd.finish import finish_atoms
             atoms, reports = finish_atoms(natoms, a, x, lat, screen=screen, cell=cell, symmetry=symmetry, dedup=dedup,
-                                          match=match)
+                                          match=match, primitive=primitive)
             for leg, report in reports.items():  # (only the legs that were asked for: the others keep their last)
                 setattr(self, "last_" + leg, report)
             return atoms

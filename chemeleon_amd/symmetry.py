@@ -19,7 +19,8 @@ set that is no group halves the tolerance, at most four times. Code 4 is "trigon
 
 This is not a port of spglib, and how far the two agree on real samples has not been measured. There is no
 reduction to a primitive cell: with n_trans > 1 the answer describes the cell as given, so a supercell whose
-lattice has lower symmetry than the primitive lattice (a 2x1x1 cell of CsCl) reports the lower system. The
+lattice has lower symmetry than the primitive lattice (a 2x1x1 cell of CsCl) reports the lower system; the way
+round it is chemeleon_amd.primitive (primitive_states, or sample(primitive=...)), which runs first. The
 space-group number and the point group's name are not built ("Crystal system with the atoms").
 """
 

@@ -941,8 +941,9 @@ int chm_cell_apply(const chm_cell* plan, const void* d_records, size_t n_record_
  *
  * Deliberately not built: the reduction to a primitive cell. When n_trans > 1 the answer describes the cell as
  * given, so a supercell whose lattice has lower symmetry than the primitive lattice (a 2x1x1 cell of CsCl)
- * reports the lower system (tetragonal); n_trans is in the record so that a caller can tell. The space-group
- * number and the point group's name are not built either.
+ * reports the lower system (tetragonal); n_trans is in the record so that a caller can tell. The way round it is
+ * chm_prim_*, below: run it first and give this run the primitive cells. The space-group number and the point
+ * group's name are not built either.
  *
  * CHM_SYMM_MISMATCH and d_require work as in the cell run, with crystal-system codes. The optional second output
  * d_ops (may be NULL with n_ops_bytes = 0) holds CHM_SYMM_MAX_OPS slots of 16 bytes per crystal: int32 candidate
@@ -990,6 +991,83 @@ int chm_symm_run(const chm_symm* plan, const void* d_cell_records, size_t n_reco
                  float angle_tolerance, void* d_out, size_t n_out_bytes, void* d_ops, size_t n_ops_bytes,
                  void* stream);
 
+/* Primitive cells of finished structures on the device: the pure translations that chm_symm_* counts as n_trans
+ * are used to reduce every crystal to a primitive cell, so that the symmetry, matching and grouping legs can be
+ * given primitive cells (a sampler asked for 8 atoms of a 2-atom compound returns supercells routinely). This is
+ * NOT a port of spglib's find_primitive: the definition below is this library's own, and how far the two agree
+ * on real samples has not been measured.
+ *
+ * Input per crystal: that of the symmetry run (the state, and the crystal's chm_cell_record from chm_cell_run on
+ * the same lattices with the same symprec and angle_tolerance).
+ *
+ * Basis. Lr = T L and x' = frac(x adj(T)), the bits of chm_cell_apply (the same device code). CHM_PRIM_NO_LATTICE
+ * and CHM_PRIM_THIN are set by the rules of CHM_SYMM_NO_LATTICE and CHM_SYMM_THIN, word for word.
+ *
+ * Pivot and candidates. The pivot atom p is chosen as in chm_symm_* (the first atom of the rarest species, ties to
+ * the smallest type); the candidate translations are t_j = x'_j - x'_p, j over that species in node order
+ * (n_pivot of them), not wrapped.
+ *
+ * Acceptance. t_j is accepted at tolerance tol when every atom i has an atom k of its type with
+ * d = (x'_i + t_j) - x'_k, d -= rintf(d) per component, c = d Lr, (c0 c0 + c1 c1) + c2 c2 <= tol tol: the
+ * acceptance test of chm_symm_* with W = I, the same device function, fp32, every operation rounded on its own.
+ * partner(i, j) is the lowest node index k among the atoms of i's type that pass this test.
+ *
+ * Group, in integers. m = the number of accepted translations. q_j = rintf((float)m t_j) mod m per component (into
+ * [0, m)), an integer triple per accepted j. Lambda = the Z-span of all q_j together with m e_0, m e_1, m e_2, and
+ * H = Lambda's row Hermite normal form: upper triangular, positive diagonal, 0 <= H[i][k] < H[k][k] for i < k.
+ * H is unique, so the order in which the q_j are reduced cannot show. It is computed on one lane in 64-bit
+ * integers.
+ *
+ * Consistency. The accepted set is consistent at tol when (a) m divides every species' atom count, (b)
+ * det H == m m (the translations are a group of order m), (c) every t_j lies within tol of q_j / m (the distance
+ * test above between t_j and the fp32 quotients (float)q / (float)m), and (d) exactly n / m atoms i have no
+ * partner(i, j) < i over the accepted j. Otherwise tol is halved (exactly, in fp32; it starts at symprec) and the
+ * search runs again, at most 4 halvings; after the last the crystal gets CHM_PRIM_AMBIGUOUS.
+ *
+ * Output. A crystal with m == 1, or with any flag, is passed through: its n atoms in node order in the reduced
+ * basis (Lr, x'), n_prim = n, H written as the identity. Otherwise Lp = H Lr / m, each entry
+ * ((h0 l0 + h1 l1) + h2 l2) / m in fp64, rounded once to fp32; the kept atoms are those of condition (d), in
+ * ascending node index, with x_p = frac(x' adj(H) / m), component k being ((x0 a[0][k] + x1 a[1][k]) + x2 a[2][k]) / m
+ * with the integer adjugate of H, fp64, rounded once, a value that rounds to 1 written as 0. There is no
+ * averaging over an orbit: the representative of an orbit is its member of the lowest node index, with the
+ * coordinates it has (a deliberate difference from spglib, which averages). The lattice Lp is a basis of the
+ * primitive lattice, not a standardised or reduced one; chm_cell_run reduces it where that is wanted.
+ *
+ * Buffers. d_out: one chm_prim_record per crystal, 64 bytes each. d_source [N] int32: per input atom its rank among
+ * the kept atoms of its crystal, or -1. d_new_offsets [B + 1] int32: the first node of every crystal in the
+ * packed output; new_offsets[B] = N', the number of rows written. d_atom_types_out [N], d_frac_out [N,3]: the
+ * packed state, crystal g's atoms at rows new_offsets[g] + rank; they are sized for the input's N and cleared
+ * first, so the rows from N' on are zero. d_lattices_out [B,3,3]. The outputs must not be the inputs.
+ * The plan holds the node offsets on the current device (create: as the symmetry plan's; more than 256 atoms in
+ * a crystal is refused with CHM_E_UNSUPPORTED). The run takes every buffer with its count (cell records and out
+ * 16-byte aligned); a NULL pointer, a mismatched count or tolerances outside the cell run's limits return
+ * CHM_E_ARG naming the argument before the first HIP call and nothing is enqueued. It allocates nothing and does
+ * not synchronise: legal under stream capture. All counts are integer sums: two runs, and a crystal alone or
+ * inside any batch, give the same bytes per crystal. */
+#define CHM_PRIM_AMBIGUOUS 1     /* no consistent set of translations after 4 halvings */
+#define CHM_PRIM_NO_LATTICE 4    /* as CHM_SYMM_NO_LATTICE */
+#define CHM_PRIM_THIN 8          /* as CHM_SYMM_THIN */
+typedef struct {
+  int32_t n_prim;             /* atoms written for this crystal: n / m, or n where it is passed through */
+  int32_t n_trans;            /* m of the deciding level (0 where no search ran) */
+  int32_t n_pivot;            /* atoms of the pivot species */
+  int32_t halvings;           /* halvings of tol used, 0..4 */
+  int32_t flags;              /* CHM_PRIM_* bits */
+  int32_t h[6];               /* H[0][0], H[0][1], H[0][2], H[1][1], H[1][2], H[2][2] */
+  float tol;                  /* the tolerance of the level that decided */
+  int32_t lattice_system;     /* of the input cell, copied from the cell record (-1 with CHM_PRIM_NO_LATTICE) */
+  int32_t reserved[3];        /* written as 0 */
+} chm_prim_record;            /* 64 bytes */
+typedef struct chm_prim chm_prim;
+int chm_prim_create(const int32_t* h_natoms, int num_graphs, chm_prim** out);
+void chm_prim_destroy(chm_prim* plan);
+int chm_prim_run(const chm_prim* plan, const void* d_cell_records, size_t n_record_bytes, const int64_t* d_atom_types,
+                 int64_t n_atom_types, const float* d_frac, int64_t n_frac, const float* d_lattices,
+                 int64_t n_lattices, float symprec, float angle_tolerance, void* d_out, size_t n_out_bytes,
+                 int32_t* d_source, int64_t n_source, int32_t* d_new_offsets, int64_t n_new_offsets,
+                 int64_t* d_atom_types_out, int64_t n_atom_types_out, float* d_frac_out, int64_t n_frac_out,
+                 float* d_lattices_out, int64_t n_lattices_out, void* stream);
+
 /* Matching finished structures against reference structures on the device: what test_structure_matching of the
  * reference's scripts/evaluate.py asks of pymatgen on the host (StructureMatcher().fit(ref_st, st), reported as
  * match rate and RMSD). This is NOT a port of pymatgen: the definition below is this library's own, and how far
@@ -1006,7 +1084,8 @@ int chm_symm_run(const chm_symm* plan, const void* d_cell_records, size_t n_reco
  * CHM_CELL_NOT_REDUCED, CHM_CELL_DEGENERATE or CHM_CELL_NONFINITE, or a reduced volume (below) is not a finite
  * number > 0. CHM_MATCH_SIZE: n != n_ref. CHM_MATCH_COMPOSITION (tested when the sizes are equal): some type's
  * atom count differs, compared as integers. Atom counts must be equal: there is no reduction to a primitive
- * cell, so a supercell sample does not match its primitive reference (a deliberate difference from pymatgen).
+ * cell, so a supercell sample does not match its primitive reference (a deliberate difference from pymatgen);
+ * the way round it is chm_prim_*, above: reduce both to primitive cells first.
  *
  * Reduced frames. Ls = T_s L and x' = frac(x adj(T_s)) for the sample, Lr and xr likewise for the reference,
  * exactly as chm_cell_apply produces them (the same device code). V_s, V_r = |det| of those fp32 cells in fp64,
