@@ -1,5 +1,5 @@
 // chm_batch: the host-side index tables and plans of a batch, its workspace layout, the batch entry points, and
-// the host-only queries that restate the tables and plans for the CPU tests (chm_debug_layer_jobs .. _pair_nodes).
+// the host-only queries that restate the tables and plans for the CPU tests (chm_debug_row_nodes .. _pair_nodes).
 #include <algorithm>
 
 #include "chm_host.h"
@@ -217,7 +217,7 @@ static long count_tiles(const BatchTables& t) {
 static long short_row_tiles(const BatchTables& t, int P, long ncu, long layer_min) {
   if (t.knn || t.E <= 0 || ncu <= 0 || P < 1) return -1;
   const long R = (t.E + kTileRows - 1) / kTileRows;
-  if (R >= layer_min) return -1;  // (the one-grid schedules take uniform tiles)
+  if (R >= layer_min) return -1;  // (the pair grid takes uniform tiles)
   for (int n : t.nat)
     if (n > kShortRows) return -1;  // (a node then spans at most two tiles)
   const long J = 2L * P, per = ncu / J;  // jobs per row tile (conditionings x column tiles); row tiles per round
@@ -269,10 +269,7 @@ static size_t batch_layout(chm_batch* b, const chm_model* m, char* base, long nt
     b->sbuf = fl((size_t)P * b->nrt * H);
     b->msgbuf = fl((size_t)P * (b->r2tot + 1) * H);
     b->rcnt = (unsigned*)carve((size_t)P * b->nrt * 8 * sizeof(unsigned));
-    b->lflags = (unsigned*)carve(b->nrt * sizeof(unsigned));
-    b->xbad = (unsigned*)carve(2 * kMaxLayers * sizeof(unsigned));  // layer l: [l]; tail of layer l: [kMaxLayers + l]
-    b->sched_cap = b->nrt + kMaxLag + 64;
-    b->sched = (unsigned*)carve((size_t)L * (16 + 8 * b->sched_cap) * sizeof(unsigned));
+    b->xbad = (unsigned*)carve(2 * kMaxLayers * sizeof(unsigned));  // layer l: [l] (the second half: unused)
   }
   if (b->knn) {  // (E = the edge capacity E_cap)
     b->cand_off = (long*)carve((B + 1) * sizeof(long));
@@ -311,7 +308,6 @@ static size_t batch_layout(chm_batch* b, const chm_model* m, char* base, long nt
     b->Hs = b->Hls = b->aggs = b->Us = nullptr;
     b->He = b->Hle = b->agge = b->Ue = nullptr;
   }
-  b->tail_flags = (unsigned*)carve(kMaxTailTiles * sizeof(unsigned));
   b->Hf = fl((size_t)P * N * H);
   b->HO = fl((size_t)P * N * HEADS_N);
   b->LAT = fl((size_t)P * B * 9);
@@ -368,22 +364,6 @@ static int batch_build(const chm_model* m, const int32_t* h_natoms, int B, int m
     return fail(CHM_E_ARG, "workspace too small or not 256-byte aligned (need " + std::to_string(need) + " bytes)");
   }
   b->bytes = batch_layout(b, m, base, b->ntiles);
-  {  // edge layer 1 tail split: whole rounds of 256x256 tiles first (needs ncu, an even count of tiles).
-     // Only for a short partial round (<= 1/4 of the CUs): 64x40 (32 of 256 tiles) gains 6% per step;
-     // at 256x40 (128 of 256) the split grid lost 0.8% (profiles/r2/split_*)
-    const long tiles1 = (t.E + kTileRows - 1) / kTileRows * (H / 256);
-    if (!t.knn && t.rt_nbig < 0 && m->ncu > 0 && tiles1 > m->ncu && tiles1 % m->ncu && (tiles1 % m->ncu) * 4 <= m->ncu) {
-      long full = tiles1 / m->ncu * m->ncu;
-      full -= full % (H / 256);
-      const long rows_a = full / (H / 256) * kTileRows;
-      int ta = 0;
-      while (ta < (int)t.tiles.size() && (t.tiles[ta].y < t.N ? t.estart[t.tiles[ta].y] : t.E) <= rows_a) ++ta;
-      if (rows_a < t.E && ta > 0 && ta < (int)t.tiles.size() && (t.E - rows_a + kTileRows - 1) / kTileRows <= kMaxTailTiles) {
-        b->l1_rows_a = rows_a;
-        b->l2_tile_a = ta;
-      }
-    }
-  }
   // index tables (setup only: the host vectors must outlive the copies, so the stream is drained)
   hipError_t e = hipSuccess;
   auto up = [&](void* dst, const void* src, size_t bytes) {
@@ -415,7 +395,6 @@ static int batch_build(const chm_model* m, const int32_t* h_natoms, int B, int m
     }
     if (e == hipSuccess && b->rcnt)  // (the counters return to 0 at the end of every launch)
       e = hipMemsetAsync(b->rcnt, 0, (size_t)b->P * b->nrt * 8 * sizeof(unsigned), s);
-    if (e == hipSuccess && b->lflags) e = hipMemsetAsync(b->lflags, 0, b->nrt * sizeof(unsigned), s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
@@ -423,19 +402,6 @@ static int batch_build(const chm_model* m, const int32_t* h_natoms, int B, int m
     return fail(CHM_E_HIP, std::string("index upload: ") + hipGetErrorString(e));
   }
   *out = b;
-  return CHM_OK;
-}
-
-extern "C" int64_t chm_debug_layer_jobs(int64_t R, int P, int lag, int64_t* out, int64_t cap) {
-  if (R < 1 || P < 1 || P > 2 || lag < 1) return fail(CHM_E_ARG, "bad arguments");
-  const long nb = edge16_layer_blocks(R, P);
-  if (out && cap >= 2 * nb) edge16_layer_jobs(R, P, lag, reinterpret_cast<long*>(out));
-  return nb;
-}
-
-extern "C" int chm_debug_layer_seq(int64_t n, int P, int lag, int64_t* out) {
-  if (n < 0 || P < 1 || P > 2 || lag < 1 || !out) return fail(CHM_E_ARG, "bad arguments");
-  edge16_seq_jobs(n, P, lag, reinterpret_cast<long*>(out));
   return CHM_OK;
 }
 

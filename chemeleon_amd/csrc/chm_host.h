@@ -40,15 +40,10 @@ struct LayerW {
 
 enum MathMode { MATH_BF16X3 = 0, MATH_F32 = 1, MATH_SPLIT16 = 2 };
 constexpr long kTileRows = 256;  // rows of the edge-GEMM tiles (gemm_bf16x3_big)
-constexpr int kMaxTailTiles = 512;  // layer-1 row tiles of a partial round (< CUs / 2)
-// k_edge16_layer only from 256 row tiles (32 per XCD) on: 64x20 (100 row tiles, 12-13 per XCD, mostly
-// inside the layer-2 lag) measured 0.186 vs 0.176 ms for the two launches; 64x40 (400) gains 5%
+// both edge layers in one grid (the pair grid) only from 256 row tiles (32 per XCD) on: at 64x20 (100 row tiles,
+// 12-13 per XCD) each XCD's job list is too short to pack (edge_block)
 constexpr long kLayerMinTiles = 256;
-constexpr int kMaxLag = 1000;  // edge_lag's upper bound (sizes the persistent one-grid kernel's row slots)
-// the persistent one-grid kernel from this many row tiles on (same-box A/B, profiles/r3/ab_*: 512x40 (3200)
-// 60.2 -> 59.2 ms per step; 64x40 (400) 8.34 -> 8.44: the per-job atomic costs more than the XCD
-// balancing gains in a short grid)
-constexpr long kDynMinTiles = 1024;
+constexpr int kMaxLag = 1000;  // edge_lag's upper bound (the pair plan's layer-2 lag, in pair tiles)
 
 }  // namespace chm
 
@@ -71,14 +66,10 @@ struct chm_model {
                          // kernels instead of splitting them in the K loop (r4; measured 0.5% slower per step,
                          // DESIGN.md §4 "Node GEMMs")
   int edge_stagger = 0;  // CHM_EDGE_STAGGER: first-round start delay of every other CU (edge16.hip)
-  int edge_split = 1;    // CHM_EDGE_SPLIT=0: no partial-round tail split of edge layer 1 (see run_decoder)
   int edge_rows = 1;     // CHM_EDGE_ROWS=0: edge layer 2 on node-aligned segment tiles instead of row tiles
-  int edge_layer = 1;    // CHM_EDGE_LAYER=0: edge layers 1 and 2 as two launches (else one grid, k_edge16_layer)
-  int edge_lag = 8;      // CHM_EDGE_LAG: its layer-2 lag behind layer 1, in row tiles per XCD (pair grid: pair tiles; r6: 8)
+  int edge_layer = 1;    // CHM_EDGE_LAYER=0: edge layers 1 and 2 as two launches (else one grid, k_edge16_pairs_grid)
+  int edge_lag = 8;      // CHM_EDGE_LAG: its layer-2 lag behind layer 1, in pair tiles (r6: 8)
   long edge_layer_min = chm::kLayerMinTiles;  // CHM_EDGE_LAYER_MIN: row tiles from which the one-grid kernel runs
-  int edge_dyn = 1;      // CHM_EDGE_DYN: one-grid kernel form, 0 static block -> job map (k_edge16_layer), 1 the
-                         // persistent form (k_edge16_layer_dyn) from kDynMinTiles row tiles on, 2 always persistent
-  int edge_pool = 15;    // CHM_EDGE_POOL: the persistent form's run-time-claimed share of the row tiles (%)
   int edge_pairs = 1;    // CHM_EDGE_PAIRS / option edge_pairs: fc edge layer 1 on unordered pairs (k_edge16_pairs:
                          // half its matrix work; both directions' S from one GEMM row), then edge layer 2
   int edge_pairs_layer = 1;  // CHM_EDGE_PAIRS_LAYER / option edge_pairs_layer: both edge layers on pairs in one
@@ -88,12 +79,11 @@ struct chm_model {
                              // (short_row_tiles, set at batch creation; bit-identical)
   int ncu = 0;          // compute units of the device the model lives on
   int device = 0;        // its HIP device ordinal (the current device at chm_model_create)
-  unsigned xcd_mask = 0; // XCC ids a grid's blocks ran on at model creation (the persistent edge kernel needs 0xff)
-  int edge_skip_xcd = -1;  // (tests) option edge_dyn_skip_xcd: the persistent kernel's blocks on that XCD exit
+  unsigned xcd_mask = 0; // XCC ids a grid's blocks ran on at model creation (the pair grid needs 0xff)
   int repair_grid = 0;   // CHM_REPAIR_GRID: blocks of the edge kernels' repair launches (default: ncu)
   int film = 1;          // 0: time_dim = text_dim = 0 (no FilmLayer: the CrystalClip graph encoder)
   const char* edge_trace = nullptr;  // CHM_EDGE_TRACE=file: one edge-GEMM launch's block timeline
-  int edge_trace_layer = 1;          // CHM_EDGE_TRACE_LAYER: 1 or 2 (two-launch schedule), 3 (k_edge16_layer), 4 (pair grid)
+  int edge_trace_layer = 1;          // CHM_EDGE_TRACE_LAYER: 1 or 2 (two-launch schedule), 4 (pair grid)
   std::vector<chm::LayerW> layers;
 };
 
@@ -128,10 +118,7 @@ struct chm_batch {
   long rt_nbig = -1;
   float *sbuf = nullptr, *msgbuf = nullptr;
   unsigned* rcnt = nullptr;
-  unsigned* lflags = nullptr;  // k_edge16_layer: per row tile (returns to 0 at the end of every launch)
-  unsigned* xbad = nullptr;    // k_edge16_layer: per layer, raised when its repair launches must run
-  unsigned* sched = nullptr;   // k_edge16_layer_dyn: per layer 16 + 8 * sched_cap words, zeroed per decoder call
-  long sched_cap = 0;
+  unsigned* xbad = nullptr;    // the pair grid: per layer, raised when its repair launches must run
   int math;     // arithmetic mode fixed at creation (copied from the model)
   // workspace
   float *cin, *cemb, *Hres, *Hl, *Y, *agg, *PQ, *gbias, *F, *S, *M, *Hf, *HO, *LAT;
@@ -144,12 +131,6 @@ struct chm_batch {
   unsigned* rowmax;  // split16: per S row, the packed int8 exponents of its four 128-column chunks, [P][E]
   void* owned = nullptr;  // the library's own allocation (chm_batch_create); null for caller workspaces
   size_t bytes = 0;
-  // edge layer 1's partial last round (split16 / k_edge16, see run_decoder): rows [0, l1_rows_a) fill
-  // whole rounds of the grid; the rest runs in one grid with edge layer 2, whose segment tiles from
-  // l2_tile_a on read those rows. 0 = no split.
-  long l1_rows_a = 0;
-  int l2_tile_a = 0;
-  unsigned* tail_flags = nullptr;  // [kMaxTailTiles] per layer-1 row tile of the partial round
   // knn (radius-graph) batches: edges rebuilt every decoder call (knn.hip); E is then the current
   // graph's edge count and E_cap the capacity the edge buffers are sized for
   int knn = 0, knn_max_nb = 20;
@@ -191,8 +172,8 @@ struct EdgePlan {
   bool ps;         // pre-split node GEMMs: the producers write the A operands split (no row-max atomics then)
   bool pairs;      // fc edge layer 1 on unordered pairs (option edge_pairs): F holds the pairs' features only
   bool pair_grid;  // both edge layers on pairs in one grid (k_edge16_pairs_grid) for this call
-  bool waits;      // a schedule with intra-grid waits: its flag words start clear in every call
-  bool zero_grid;  // the pair grid's repair requests and per-layer flags: zeroed by the embedding launch
+  bool zero_grid;  // the pair grid's repair requests and per-layer flags start clear in every call: zeroed by the
+                   // embedding launch
 };
 
 // profiling (decoder.hip, chm_prof_*): a pair of events around the launches of a scope, while enabled

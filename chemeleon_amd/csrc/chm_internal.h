@@ -103,17 +103,8 @@ struct EdgeArgs {
   // batch (rinfo [ntiles][kRowInfo] {node, rows | first row << 10 | kind << 20}, rinfo_n [ntiles] entries),
   // so the epilogue loads it in one round trip instead of deriving it through dependent loads; or null
   const int2* rinfo; const int* rinfo_n;
-  // k_edge16_layer (both edge layers in one grid): per row tile, the count of layer-1 column tiles that
-  // have written S through, then of the layer-2 tiles that have read it (the last one resets it to 0)
-  unsigned* lflags;
-  unsigned* xbad;  // k_edge16_layer: raised by a layer-2 tile that read S of another XCD or whose wait timed
-                   // out; k_edge16_tail: raised by a segment tile whose wait for this grid's layer-1 tiles
-                   // timed out. Either way the repair launches behind the grid recompute the layer.
-  // k_edge16_tail: per layer-1 row tile from flag_row0 on, the count of its finished column tiles
-  // (EPI_EDGE bumps, EPI_SEGMEAN tiles reading rows >= flag_row0 wait); null = no intra-grid waits.
-  // zero_flags / nzero: an EPI_EDGE launch's block 0 clears them for the next grid.
-  unsigned* flags; long flag_row0;
-  unsigned* zero_flags; int nzero;
+  unsigned* xbad;  // the pair grid (k_edge16_pairs_grid): raised by a layer-2 job that read S of another XCD or whose
+                   // wait timed out; the repair launches behind the grid then recompute the layer
   // edge layer 1 on unordered pairs (k_edge16_pairs, fc batches, option edge_pairs): A = the pairs' Fourier
   // features (Mp rows: per crystal the pairs i <= j, row-major), pi / pj = the pair's nodes, pe = its edge
   // rows {(i, j), (j, i)} (equal for i == j)
@@ -127,18 +118,16 @@ struct EdgeArgs {
             // barriers, bit 2 = no epilogue stores (EDGE / SEGMEAN); k_edge16 also: bit 3 = no SiLU (SEGMEAN),
             // bit 4 = main loop only (no epilogue), bit 5 = no segment sums (SEGMEAN); bit 6 (tests, exact
             // results) = row tiles never wait for the previous tile's partial sums (msgbuf path); bit 9
-            // (tests, exact results) = k_edge16_layer's layer-2 tiles always request the repair launches;
-            // bit 13 (tests, exact results) = k_edge16_tail's layer-1 tiles start ~10 ms late and its
-            // segment tiles wait ~2^10 spins only (a real timeout: they read S before it is written);
-            // bit 14 (profiling / tests, WRONG results after a failed check) = no repair launches behind
-            // k_edge16_tail or k_edge16_layer; bits 15 / 16 (profiling) = layer-1 / layer-2 tiles read their A
-            // rows from the first 16 row tiles (L2-resident)
+            // (tests, exact results) = the pair grid's layer-2 jobs always request the repair launches;
+            // bit 14 (profiling / tests, WRONG results after a failed check) = no repair launches behind the pair
+            // grid; bits 15 / 16 (profiling) = layer-1 / layer-2 tiles read their A rows from the first 16 row
+            // tiles (L2-resident)
 };
 // Device event counters of the edge kernels (edge16.hip), cumulative over launches and graph replays
 // until chm_prof_events_reset: wait timeouts and repair launches that ran (each must read 0 in a
 // healthy run; a repair doubles the cost of its layer).
-enum { EV_LAYER_TIMEOUT = 0, EV_LAYER_XCD = 1, EV_LAYER_REPAIR = 2, EV_TAIL_TIMEOUT = 3, EV_TAIL_REPAIR = 4,
-       EV_LAYER_INCOMPLETE = 5, EV_COUNT = 8 };
+// (slots 3 - 5 counted the tail grid and the persistent one-grid kernel, both removed: reserved, always 0)
+enum { EV_LAYER_TIMEOUT = 0, EV_LAYER_XCD = 1, EV_LAYER_REPAIR = 2, EV_COUNT = 8 };
 // the XCD ids (bit x = XCC_ID x) the blocks of a `blocks`-block grid ran on (synchronous; model creation)
 hipError_t xcd_mask(int blocks, unsigned* out);
 hipError_t edge_events_read(unsigned long long* out);  // EV_COUNT values
@@ -172,18 +161,6 @@ hipError_t train_noise(const TrainArgs& g, hipStream_t s);
 hipError_t train_loss(const TrainArgs& g, hipStream_t s);
 // the split16 edge GEMMs on v_mfma_f32_16x16x32_f16 (edge16.hip; S / W2 column permutation 2)
 hipError_t edge_gemm16(const EdgeArgs& g, int epi, hipStream_t s);
-// one grid: edge layer 1 (EPI_EDGE, g1: a row range) first, then edge layer 2 (EPI_SEGMEAN, g2: segment
-// tiles that read none of g1's rows)
-// g2.xbad: raised on a timed-out wait; the repair launches behind the grid then recompute layer 2
-hipError_t edge_gemm16_tail(const EdgeArgs& g1, const EdgeArgs& g2, int repair_grid, hipStream_t s);
-// both edge layers in one grid (row tiles; layer-2 tiles of row tile i - lag behind layer 1's row tile i)
-// sched != null: the persistent form (grid blocks; the last pool% of the row tiles claimed at run time;
-// sched = the layer's zeroed scheduling words, 16 + 8 * cap, cap >= R + lag + 64)
-hipError_t edge_gemm16_layer(const EdgeArgs& g1, const EdgeArgs& g2, int lag, int repair_grid, hipStream_t s,
-                             unsigned* sched = nullptr, int cap = 0, int grid = 0, int pool = 15, int skip_xcd = -1);
-void edge16_seq_jobs(long n, int P, int D, long* out);  // (host) the persistent form's per-XCD job sequence
-long edge16_layer_blocks(long R, int P);                        // its grid size
-void edge16_layer_jobs(long R, int P, int D, long* out);         // (host) its block -> job map
 hipError_t edge16_init();
 // edge layer 1 on unordered pairs: S rows of both directions of every pair from one GEMM row (edge16.hip)
 hipError_t edge_gemm16_pairs(const EdgeArgs& g, hipStream_t s);

@@ -112,8 +112,8 @@ static hipError_t run_edge_gemm(const chm_batch* b, GemmArgs g, int epi, const v
   return gemm_bf16x3_big(g, epi, s);
 }
 
-// profiling (CHM_EDGE_TRACE=file, CHM_EDGE_TRACE_LAYER=1-4): the 4th eager launch of edge layer
-// 1 or 2 records {hw id, t0, t_mainloop, t_end, ...} per block (s_memrealtime), dumped to the file
+// profiling (CHM_EDGE_TRACE=file, CHM_EDGE_TRACE_LAYER=1, 2 or 4): the 4th eager launch of edge layer
+// 1 or 2 (4: of the pair grid) records {hw id, t0, t_mainloop, t_end, ...} per block (s_memrealtime), dumped to the file
 template <class F>
 static hipError_t traced_edge_launch(const chm_model* m, EdgeArgs& ea, int which, long E, hipStream_t s, F&& launch) {
   static std::atomic<int> traced{0};
@@ -122,8 +122,8 @@ static hipError_t traced_edge_launch(const chm_model* m, EdgeArgs& ea, int which
                   hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusNone && ++traced == 4;
   if (!tr) return launch();
   unsigned long long* tbuf = nullptr;
-  // (3: slot 8 k + XCD; 4, the pair grid: 8 x its longest job list, at most E / 32 jobs)
-  const long tblocks = (which == 4 ? E / 4 : which == 3 ? 48 * (E / 256 + 1) : 4 * (E / 128 + 1)) + 4096;
+  // (4, the pair grid: 8 x its longest job list, at most E / 32 jobs)
+  const long tblocks = (which == 4 ? E / 4 : 4 * (E / 128 + 1)) + 4096;
   hipError_t e = hipMalloc(&tbuf, tblocks * 48);
   if (e == hipSuccess) e = hipMemsetAsync(tbuf, 0, tblocks * 48, s);
   if (e != hipSuccess) return e;
@@ -204,24 +204,14 @@ EdgePlan edge_plan(const chm_batch* b, int P) {
   // the memsets cost 4.8 us each per call, 0.9% of a 64x20 step)
   p.pair_grid = p.pairs && m->edge_pairs_layer && m->edge_rows && b->rtiles && m->edge_layer && b->psched &&
                 P == b->P && b->nrt >= m->edge_layer_min && m->ncu > 0 && m->xcd_mask == 0xffu && b->rt_nbig < 0;
-  p.waits = !p.pairs || p.pair_grid;
   p.zero_grid = b->xbad && b->math == MATH_SPLIT16 && p.pair_grid;
   return p;
 }
 
-// k_edge16_layer / k_edge16_tail: repair requests (layer l: xbad[l], tail of layer l: xbad[kMaxLayers + l])
-// and row-tile flags start clear in every call (the flags also return to 0 at the end of every
-// launch; this keeps a timed-out wait from leaking into later calls). The pair grid's words (zero_grid) are
-// cleared by run_decoder's embedding launch; grid_too: here as well (chm_debug_edge_layer has no such launch).
+// The pair grid's repair requests (layer l: xbad[l]) and per-layer flags (zero_grid) start clear in every call:
+// run_decoder's embedding launch clears them; grid_too: this does (chm_debug_edge_layer has no such launch).
 int clear_edge_flags(chm_batch* b, const EdgePlan& ep, hipStream_t s, bool grid_too) {
-  const chm_model* m = b->m;
-  const int L = m->d.num_layers;
-  if (b->xbad && b->math == MATH_SPLIT16 && ep.waits && !ep.pair_grid) {
-    HIPCHK(hipMemsetAsync(b->xbad, 0, 2 * kMaxLayers * sizeof(unsigned), s));
-    if (!ep.pairs && m->edge_rows && m->edge_layer && m->edge_dyn && b->sched)
-      HIPCHK(hipMemsetAsync(b->sched, 0, (size_t)L * (16 + 8 * b->sched_cap) * sizeof(unsigned), s));
-    if (!ep.pairs && m->edge_rows && m->edge_layer) HIPCHK(hipMemsetAsync(b->lflags, 0, b->nrt * sizeof(unsigned), s));
-  }
+  const int L = b->m->d.num_layers;
   if (grid_too && ep.zero_grid) {
     HIPCHK(hipMemsetAsync(b->xbad, 0, 2 * kMaxLayers * sizeof(unsigned), s));
     HIPCHK(hipMemsetAsync(b->psched, 0, (size_t)L * 8 * b->pplan.npx * sizeof(unsigned), s));
@@ -300,10 +290,6 @@ int edge_block(chm_batch* b, int P, int l, const EdgePlan& ep, bool ps, hipStrea
       gs.rt_e0 = b->rt_nbig * kTileRows;
       return edge_gemm16(gs, EPI_SEGMEAN, s);
     };
-    // (instrumented eager launches keep one launch per layer, so the per-kernel timings stay whole;
-    // captured launches are never instrumented)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool instrumented = g_prof_on && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
     // (same-box A/B, static grid against two launches: 64x40 8.47 -> 7.77 ms per step, 512x40 54.9 -> 54.8,
     // 64x20 2.95 -> 3.10: 100 row tiles leave each XCD's job list too short to pack; profiles/r5/grid/)
     if (pair_grid) {
@@ -333,40 +319,6 @@ int edge_block(chm_batch* b, int P, int l, const EdgePlan& ep, bool ps, hipStrea
       }
       ProfScope ps(CHM_K_EDGE_MESSAGE, s);
       HIPCHK(layer2(e2));
-    } else if (e2.rtiles && m->edge_layer && b->nrt >= m->edge_layer_min && b->rt_nbig < 0 &&
-               (!m->edge_trace || m->edge_trace_layer == 3)) {
-      // both layers in one grid: layer 2's row tiles behind layer 1's (k_edge16_layer)
-      e1.lflags = e2.lflags = b->lflags;
-      e1.xbad = e2.xbad = b->xbad + l;
-      ProfScope ps(CHM_K_EDGE_LAYER, s);
-      // (CHM_EDGE_TRACE_LAYER=3: block timelines of this grid, slot = blockIdx)
-      HIPCHK(traced_edge_launch(m, e1, 3, E, s, [&] {
-        e2.trace = e1.trace;
-        const hipError_t r =
-            m->ncu > 0 && m->xcd_mask == 0xffu &&
-                    (m->edge_dyn == 2 || (m->edge_dyn == 1 && b->nrt >= kDynMinTiles))
-                ? edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s,
-                                    b->sched + (size_t)l * (16 + 8 * b->sched_cap), (int)b->sched_cap, m->ncu,
-                                    m->edge_pool, m->edge_skip_xcd)
-                : edge_gemm16_layer(e1, e2, m->edge_lag, m->repair_grid, s);
-        e2.trace = nullptr;
-        return r;
-      }));
-    } else if (b->l1_rows_a > 0 && b->xbad && m->edge_split && !instrumented && !m->edge_trace) {
-      // Edge layer 1 in whole rounds of the grid (rows [0, l1_rows_a)), then one grid with its
-      // partial last round first and all of edge layer 2's segment tiles behind it (the few that
-      // read those rows wait for them inside the grid). Same tiles, same arithmetic: bit-identical
-      // to one launch per layer.
-      EdgeArgs e1b = e1;
-      e1.M = b->l1_rows_a;
-      e1.zero_flags = b->tail_flags;
-      e1.nzero = (int)((E - b->l1_rows_a + kTileRows - 1) / kTileRows);
-      e1b.row_base = b->l1_rows_a;
-      e1b.flags = e2.flags = b->tail_flags;
-      e1b.flag_row0 = e2.flag_row0 = b->l1_rows_a;
-      e2.xbad = b->xbad + kMaxLayers + l;  // (a timed-out wait: the repair launches recompute edge layer 2)
-      HIPCHK(edge_gemm16(e1, EPI_EDGE, s));
-      HIPCHK(edge_gemm16_tail(e1b, e2, m->repair_grid, s));
     } else {
       {
         ProfScope ps(CHM_K_EDGE_FOURIER, s);

@@ -307,51 +307,18 @@ struct KLoop {
 
 }  // namespace
 
-// k_edge16_layer's block -> job map (host and device: chm_debug_layer_jobs tests it). XCD x = b % 8
-// walks row tiles [R x / 8, R (x + 1) / 8) as groups i = 0 .. n + d - 1: layer-1 tiles (i, 0), (i, 1)
-// while i < n, then the layer-2 tiles of row tile i - d (P conditionings x 2 column tiles) from i = d.
-// kind 0 = no job (padding), 1 = layer 1 with tile index bid = row tile * 2 + column tile, 2 = layer 2
-// with bid = (row tile * P + conditioning) * 2 + column tile.
-struct LayerJob { int kind; long bid; };
-__host__ __device__ inline LayerJob layer_job(long b, long R, int P, int D) {
-  const long x = b & 7, k = b >> 3;
-  const long lo = R * x / 8, hi = R * (x + 1) / 8, n = hi - lo;
-  const long G = 2 + 2L * P, d = D < n ? D : n;
-  long i, s;
-  if (k < 2 * d) {
-    i = k / 2;
-    s = k % 2;
-  } else if (k - 2 * d < (n - d) * G) {
-    i = d + (k - 2 * d) / G;
-    s = (k - 2 * d) % G;
-  } else {
-    const long k2 = k - 2 * d - (n - d) * G;
-    if (k2 >= d * 2 * P) return LayerJob{0, 0};
-    i = n + k2 / (2 * P);
-    s = 2 + k2 % (2 * P);
-  }
-  if (s < 2) return LayerJob{1, (lo + i) * 2 + s};
-  return LayerJob{2, ((lo + i - d) * P + (s - 2) / 2) * 2 + (s - 2) % 2};
-}
-
 // one output tile: virtual block vb of nvb (the XCD-aware remap turns it into a tile index), or the
-// tile index itself (bid_in >= 0). ONE (k_edge16_layer, both edge layers in one grid): layer-2 tiles
-// wait for the layer-1 tiles of their rows (EdgeArgs::lflags) and read S through the XCD's L2, which
-// is coherent only if those layer-1 tiles ran on the same XCD: the layer-1 tiles record their XCD in
-// the flag word and a layer-2 tile that finds another one raises *xbad (the runtime's repair launches
-// then recompute the layer).
+// tile index itself (bid_in >= 0: the pair grid's layer-2 jobs).
 // RG: 16-row groups per wave (4: 256-row tiles; 3: edge layer 2's 192-row tiles, k_edge16_short). The operand
 // staging loads 256 A rows either way (the rows past a short tile are read, never used).
-template <int EPI, bool ASC, bool ONE = false, int RG = 4>
-__device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb, long bid_in = -1, int tid_in = -1) {
-  static_assert(RG == 4 || (RG == 3 && EPI == EPI_SEGMEAN && !ONE), "short row tiles: edge layer 2's own launch");
+template <int EPI, bool ASC, int RG = 4>
+__device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb, long bid_in = -1) {
+  static_assert(RG == 4 || (RG == 3 && EPI == EPI_SEGMEAN), "short row tiles: edge layer 2's own launch");
   // (the node-list fallback below places tile t at row 256 t, which a mixed tiling's short tiles are not)
   static_assert(RG == 4 || kSegTable, "short row tiles read their node list from the host-built table");
   constexpr int RW = 16 * RG;  // rows per wave row (wm)
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  // (tid_in >= 0: the persistent kernel's opaque copy of threadIdx.x, so its loop does not hoist the
-  // tile's index math out of the loop and keep it in registers)
-  const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int l16 = lane & 15, g4 = lane >> 4;
   const int ntn = g.N / BN;
@@ -408,67 +375,6 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
   // (dbg 32768 / 65536, profiling: layer-1 / layer-2 tiles read their A rows from the first 16 row tiles,
   // which stay L2-resident: the launch time without the A operand's HBM misses)
   const bool a_l2 = (EPI == EPI_EDGE && (g.dbg & 32768)) || (EPI == EPI_SEGMEAN && (g.dbg & 65536));
-
-
-  if (EPI == EPI_EDGE && g.zero_flags && vb == 0 && tid < g.nzero) g.zero_flags[tid] = 0u;  // (for the next grid)
-  if (EPI == EPI_EDGE && g.flags && (g.dbg & 8192))  // (tests: the segment tiles' waits time out)
-    for (int k = 0; k < 2500; ++k) __builtin_amdgcn_s_sleep(127);
-  if (EPI == EPI_SEGMEAN && g.flags) {
-    // k_edge16_tail: a segment tile whose edge rows reach into [flag_row0, E) waits until the layer-1
-    // tiles of this grid that write those rows (dispatched first, never waiting themselves) have
-    // published them, then acquires at agent scope before any load of S or its exponents. The spin
-    // is bounded (~0.3 s), so a broken invariant can never hang the device.
-    // A wait that times out raises *g.xbad (and counts EV_TAIL_TIMEOUT): this tile then goes on with S
-    // that may not be written, and the repair launches behind the grid recompute edge layer 2.
-    const long e0 = row0 - (long)seg_c * g.E, e1 = e0 + nrows;
-    if (e1 > g.flag_row0) {
-      if (tid == 0) {
-        const long lo = (e0 > g.flag_row0 ? e0 : g.flag_row0) - g.flag_row0, hi = e1 - 1 - g.flag_row0;
-        const unsigned need = (unsigned)(g.N / BN);
-        const unsigned limit = (g.dbg & 8192) ? (1u << 10) : (1u << 21);
-        bool late = false;
-        for (long r = lo / BM; r <= hi / BM; ++r) {
-          unsigned spins = 0;
-          while (__hip_atomic_load(g.flags + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need && spins < limit) {
-            ++spins;
-            __builtin_amdgcn_s_sleep(4);
-          }
-          late |= spins >= limit;
-        }
-        if (late && g.xbad) {
-          __hip_atomic_store(g.xbad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          count_event(EV_TAIL_TIMEOUT);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      __syncthreads();
-    }
-  }
-
-  if constexpr (ONE && EPI == EPI_SEGMEAN) {
-    // k_edge16_layer: wait (bounded) until both layer-1 column tiles of these rows have stored S and
-    // its exponents (flag word: count in bits 0-7, each layer-1 tile's XCD + 1 in bits 8 + 4 n0), check
-    // that they ran on this XCD, then count this tile as a consumer (the last of the 2 P resets it)
-    if (tid == 0) {
-      unsigned* f = g.lflags + rtile;
-      const unsigned need = (unsigned)(g.N / BN);
-      unsigned spins = 0, v;
-      while (((v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 0xffu) < need &&
-             ++spins < (1u << 21))
-        __builtin_amdgcn_s_sleep(4);
-      const unsigned me = xcc_id() + 1u;
-      const bool timeout = (v & 0xffu) < need, other = ((v >> 8) & 15u) != me || ((v >> 12) & 15u) != me;
-      if (timeout || other || (g.dbg & 512))
-        __hip_atomic_store(g.xbad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (timeout) count_event(EV_LAYER_TIMEOUT);
-      else if (other) count_event(EV_LAYER_XCD);
-      const unsigned last = need + 2u * (unsigned)g.npairs - 1u;
-      if ((__hip_atomic_fetch_add(f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffu) == last)
-        __hip_atomic_store(f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    stamp(4);  // (traces of this grid: slot 4 = the wait for the layer-1 tiles is over)
-  }
 
   // ---- row exponents of the A chunks (edge layer 2): the lane's RG rows
   int ex[RG];
@@ -745,26 +651,6 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
       all(Tr{});
     else
       all(F{});
-    if constexpr (ONE) {
-      // k_edge16_layer: every store of this tile has reached the XCD's L2; count the column tile and
-      // record this XCD for the layer-2 tiles' check
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0)
-        __hip_atomic_fetch_add(g.lflags + (row0 / BM), 1u + ((xcc_id() + 1u) << (8 + 4 * (n0 / BN))), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (g.flags) {
-      // k_edge16_tail: publish this tile (S rows + exponents) to the segment tiles of the same grid
-      // that read it: every wave's stores have reached L2, one agent-scope release writes the XCD's
-      // L2 back, then the tile's counter is bumped (one per column tile)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __hip_atomic_fetch_add(g.flags + (row0 - g.flag_row0) / BM, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
     stamp_end();
     return;
   }
@@ -837,9 +723,9 @@ __device__ __forceinline__ void edge16_tile(const EdgeArgs& g, long vb, long nvb
 #pragma unroll
       for (int i = 0; i < RG; ++i) asm volatile("" : "+v"(acc[i][j])::"memory");
     }
-    if (!ONE) stamp(4);
+    stamp(4);
     for (int half = 0; half < 2; ++half) {
-      if (half == 1 && !ONE) stamp(5);
+      if (half == 1) stamp(5);
       if (wn == half) {
 #pragma unroll
         for (int i = 0; i < RG; ++i)
@@ -991,175 +877,10 @@ __global__ __launch_bounds__(512, 1) void k_edge16(EdgeArgs g) {
 // the second launch of a mixed row tiling, whose 256-row tiles fill whole rounds of the CUs and whose short tiles
 // take the partial last round (batch.hip short_row_tiles)
 __global__ __launch_bounds__(512, 1) void k_edge16_short(EdgeArgs g) {
-  if constexpr (kSegTable) edge16_tile<EPI_SEGMEAN, true, false, 3>(g, blockIdx.x, gridDim.x);
+  if constexpr (kSegTable) edge16_tile<EPI_SEGMEAN, true, 3>(g, blockIdx.x, gridDim.x);
 }
 
-// Edge layer 1's partial last round and edge layer 2 in one grid: blocks [0, nb1) are layer-1 tiles
-// (g1, rows [g1.row_base, g1.M)), the rest are all of edge layer 2's segment tiles (g2). Workgroups
-// are dispatched in index order on every XCD, so the layer-1 tiles start first and the layer-2 tiles
-// fill the CUs they leave idle; the few segment tiles that read layer-1 rows of this grid (the last
-// ones of the tile order) wait for them through g1.flags / g2.flags (edge16_tile). nb1 is a multiple
-// of 8 (blocks past the layer-1 tiles return at once), so the layer-2 part keeps its XCD-aware order.
-__global__ __launch_bounds__(512, 1) void k_edge16_tail(EdgeArgs g1, EdgeArgs g2, int nb1, int nt1) {
-  if ((int)blockIdx.x < nb1) {
-    if ((int)blockIdx.x < nt1) edge16_tile<EPI_EDGE, false>(g1, blockIdx.x, nt1);
-  } else {
-    edge16_tile<EPI_SEGMEAN, true>(g2, blockIdx.x - nb1, gridDim.x - nb1);
-  }
-}
-
-// Both edge layers of a CSP layer in one grid (fc batches on row tiles): every XCD (blockIdx % 8) walks
-// its own contiguous range of row tiles, layer-1 tiles (2 column tiles) of row tile i interleaved with
-// the layer-2 tiles (P conditionings x 2 column tiles) of row tile i - D, so a layer-2 tile normally
-// starts after the layer-1 tiles it reads have finished, and the two layers' phases (layer 1's
-// epilogue store bursts, layer 2's MFMA-bound main loop) overlap across the CUs instead of every CU
-// storing at once. Dependencies only point to earlier blocks of the same XCD's sequence (dispatched
-// in index order), and the waits are bounded.
-__global__ __launch_bounds__(512, 1) void k_edge16_layer(EdgeArgs g1, EdgeArgs g2, int R, int D) {
-  const LayerJob j = layer_job(blockIdx.x, R, g2.npairs, D);
-  if (j.kind == 1)
-    edge16_tile<EPI_EDGE, false, true>(g1, blockIdx.x, gridDim.x, j.bid);
-  else if (j.kind == 2)
-    edge16_tile<EPI_SEGMEAN, true, true>(g2, blockIdx.x, gridDim.x, j.bid);
-}
-
-// The persistent form of k_edge16_layer (option edge_layer_dyn; the default from kDynMinTiles row tiles
-// on): one block per CU, each looping over jobs of its XCD's sequence (an atomic per job on the XCD's
-// counter). The sequence has the static map's group structure (layer-1 tiles of local row i interleaved
-// with the layer-2 tiles of local row i - D; seq_job). XCD x's first ns local rows are its static rows
-// x ns .. (x + 1) ns - 1; the rest of the grid's row tiles, [8 ns, R) (edge_pool percent), form a pool
-// its later local rows claim from at run time through one counter shared by all XCDs, so an XCD that
-// runs faster claims more of them (with the static map every XCD gets R / 8 rows and the slowest one
-// sets the launch time: the XCDs' last blocks ended 240 us apart in a 4.8 ms launch at 512x40,
-// profiles/r3/traces). Per layer and launch (zeroed per decoder call): sched[x] the jobs taken on XCD x,
-// sched[8] the pool rows claimed, and the slots sched[16 + x * cap + i] of XCD x's pool rows (0 = not
-// yet resolved, row + 1, or ~0u = no row). Claims go in local-row order (the claim of row i waits for
-// row i-1's), so each XCD's valid rows are a prefix: a block that takes a layer-2 job of an invalid row
-// knows every later job of its XCD is invalid and exits; a layer-1 job of an invalid row is skipped.
-// Every wait is for a job taken earlier by a running block (deadlock-free whatever the residency), and
-// bounded: a timed-out wait raises the layer's repair request.
-struct SeqJob { int kind; long row; int sub; };  // kind 1: layer 1 (sub = column tile), 2: layer 2 (sub = cond * 2 + col)
-// Job k of an XCD's sequence: the first 2D jobs are the layer-1 tiles of local rows 0 .. D-1, then groups
-// i = D, D+1, ... of [layer 1 of row i (2 jobs), layer 2 of row i - D (2P)] (the static map's pattern,
-// unbounded). Measured and not kept: the pool rows' layer-1 tiles running ahead twice as fast (so
-// that a backlog of layer-2 tiles covers the last row's layer-1 + layer-2 chain at the end): 512x40
-// 59.2 -> 60.6 ms per step (profiles/r3/ab/ab_ra64/, ab_ra512/).
-__host__ __device__ inline SeqJob seq_job(long k, int P, int D) {
-  const long G = 2 + 2L * P;
-  if (k < 2L * D) return SeqJob{1, k / 2, (int)(k % 2)};
-  const long q = k - 2L * D, i = D + q / G;
-  const int sub = (int)(q % G);
-  if (sub < 2) return SeqJob{1, i, sub};
-  return SeqJob{2, i - D, sub - 2};
-}
-
-namespace {
-__device__ __forceinline__ unsigned wait_slot(const unsigned* p, bool& late) {
-  unsigned v, spins = 0;
-  while ((v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u && spins < (1u << 20)) {
-    ++spins;
-    __builtin_amdgcn_s_sleep(2);
-  }
-  if (v == 0u) late = true;
-  return v;
-}
-}  // namespace
-
-// (A static row's job costs only the XCD counter's atomic, about what the hardware dispatch of a block
-// of the static map costs; claiming every row from the pool measured slower: 512x40 58.15 vs 57.9 ms
-// per step at edge_pool 30 vs 15.)
-// skip_x >= 0 (tests only, option edge_dyn_skip_xcd): the blocks on XCD skip_x exit at once, as if that
-// XCD did not exist, so the self-check below must catch it.
-__global__ __launch_bounds__(512, 1) void k_edge16_layer_dyn(EdgeArgs g1, EdgeArgs g2, int R, int D, unsigned* sched,
-                                                             int cap, int ns, int skip_x) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const unsigned x = xcc_id();
-  const int P = g2.npairs;
-  unsigned* slots = sched + 16 + (long)x * cap;  // local row ns + i -> slots[i]
-  unsigned long long* done = reinterpret_cast<unsigned long long*>(sched + 10);  // finished layer-2 tiles | exits << 32
-  int* bc = reinterpret_cast<int*>(lds);
-  for (;;) {
-    if (threadIdx.x == 0) {
-      const long k = (long)__hip_atomic_fetch_add(sched + x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const SeqJob j = seq_job(k, P, D);
-      int code = 0;  // 0 = exit, 1 = layer 1, 2 = layer 2, 3 = skip
-      unsigned v = 0;  // the row + 1, ~0u = none
-      bool late = false;
-      const long jd = j.row - ns;  // pool slot of a local row past the static ones
-      if ((int)x == skip_x) {
-        code = 0;
-      } else if (jd >= cap) {
-        v = ~0u;  // (beyond every possible row: its layer-2 row is invalid too)
-      } else if (jd < 0) {
-        v = (unsigned)(x * ns + j.row) + 1u;
-      } else if (j.kind == 1 && j.sub == 0) {  // claim, after the previous local row's claim (valid rows: a prefix)
-        const unsigned prev = jd > 0 ? wait_slot(slots + jd - 1, late) : 1u;
-        v = ~0u;
-        if (prev != ~0u && prev != 0u) {
-          const unsigned r = (unsigned)(8 * ns) + __hip_atomic_fetch_add(sched + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (r < (unsigned)R) v = r + 1u;
-        }
-        __hip_atomic_store(slots + jd, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        v = wait_slot(slots + jd, late);
-        if (v == 0u) v = ~0u;
-      }
-      long bid = 0;
-      if ((int)x == skip_x) {
-      } else if (j.kind == 1) {
-        code = v == ~0u ? 3 : 1;
-        bid = (long)(v - 1u) * 2 + j.sub;
-      } else {
-        code = v == ~0u ? 0 : 2;
-        bid = ((long)(v - 1u) * P + j.sub / 2) * 2 + (j.sub & 1);
-      }
-      if (code == 0) {
-        // Exit. Self-check: the static rows of an XCD that does not exist (a device or
-        // partition mode with fewer than 8 XCDs) would never be computed. Layer-2 tiles add 1 to
-        // done[0] as they finish and exiting blocks add 2^32; the last block out sees every finished
-        // tile in the same word (one location: its coherence order holds every block's finish before
-        // its exit) and raises the repair request if any layer-2 tile is missing.
-        const unsigned long long old = __hip_atomic_fetch_add(done, 1ull << 32, __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT);
-        if ((old >> 32) + 1ull == (unsigned long long)gridDim.x &&
-            (old & 0xffffffffull) != (unsigned long long)R * P * 2) {
-          __hip_atomic_store(g2.xbad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          count_event(EV_LAYER_INCOMPLETE);
-        }
-      }
-      if (late) {  // (never in a healthy run: the layer is recomputed by the repair launches)
-        __hip_atomic_store(g2.xbad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        count_event(EV_LAYER_TIMEOUT);
-      }
-      bc[0] = code;
-      bc[1] = (int)bid;
-      bc[2] = (int)(8 * k + x);
-    }
-    __syncthreads();
-    const int code = bc[0], bid = bc[1], vb = bc[2];
-    __syncthreads();
-    if (code == 0) break;
-    if (code == 3) continue;  // (a layer-1 job of a row past the end: no tile)
-    // (the tiles read their arguments through laundered kernarg pointers: otherwise the compiler keeps
-    // both argument blocks in SGPRs across the loop and spills them)
-    typedef const __attribute__((address_space(4))) char* kptr;
-    kptr kp = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kp));
-    constexpr long off2 = (sizeof(EdgeArgs) + alignof(EdgeArgs) - 1) / alignof(EdgeArgs) * alignof(EdgeArgs);
-    const EdgeArgs* a1 = (const EdgeArgs*)(const __attribute__((address_space(4))) EdgeArgs*)kp;
-    const EdgeArgs* a2 = (const EdgeArgs*)(const __attribute__((address_space(4))) EdgeArgs*)(kp + off2);
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    if (code == 1)
-      edge16_tile<EPI_EDGE, false, true>(*a1, vb, 0, bid, tid);
-    else
-      edge16_tile<EPI_SEGMEAN, true, true>(*a2, vb, 0, bid, tid);
-    __syncthreads();
-    if (code == 2 && threadIdx.x == 0) __hip_atomic_fetch_add(done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// The XCDs a grid's blocks run on (bit x = XCC_ID x), for the persistent kernel's 8-XCD assumption.
+// The XCDs a grid's blocks run on (bit x = XCC_ID x), for the pair grid's 8-XCD assumption.
 __global__ void k_xcd_probe(unsigned* mask) {
   if (threadIdx.x == 0) atomicOr(mask, 1u << xcc_id());
 }
@@ -1178,26 +899,21 @@ hipError_t xcd_mask(int blocks, unsigned* out) {
   return e != hipSuccess ? e : ef;
 }
 
-// Repair of a k_edge16_layer launch whose check failed (*g.xbad != 0: some layer-2 tile read S written
-// on another XCD, so its L2 view may have been stale): one layer on the two-launch schedule, grid-
-// stride over the tiles so that the normal case (nothing to repair) costs one small grid that exits.
-// The layer-1 pass also clears the layer's agg row maxima (the failed launch may have max-ed garbage).
-// ev >= 0: count the repair (block 0) as that event.
-// (The layer-1 pass also clears the row-tile partial-sum counters rcnt: when a launch ended with tiles
-// that never ran, k_edge16_layer_dyn with an XCD missing, a head tile's count has no partner left.)
+// The pair grid's second repair launch (exits at once unless the grid raised its repair request, *g.xbad != 0: some
+// layer-2 job read S written on another XCD, so its L2 view may have been stale, or its wait timed out): edge layer 2
+// without intra-grid waits, grid-stride over the tiles so that the normal case (nothing to repair) costs one small
+// grid that exits. Block 0 counts the repair (EV_LAYER_REPAIR).
 template <int EPI, bool ASC>
-__global__ __launch_bounds__(512, 1) void k_edge16_repair(EdgeArgs g, long nvb, unsigned* agg_max, long nmax,
-                                                          unsigned* lflags, long nrt, int ev, unsigned* rcnt = nullptr,
-                                                          long nrcnt = 0) {
+__global__ __launch_bounds__(512, 1) void k_edge16_repair(EdgeArgs g, long nvb) {
   if (__hip_atomic_load(g.xbad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
-  if (ev >= 0 && blockIdx.x == 0 && threadIdx.x == 0) count_event(ev);
-  if (EPI == EPI_EDGE) {  // (and the row-tile flags, in case a wait timed out; null pointers come with 0 counts)
-    for (long k = (long)blockIdx.x * 512 + threadIdx.x; agg_max && k < nmax; k += (long)gridDim.x * 512) agg_max[k] = 0u;
-    for (long k = (long)blockIdx.x * 512 + threadIdx.x; lflags && k < nrt; k += (long)gridDim.x * 512) lflags[k] = 0u;
-    for (long k = (long)blockIdx.x * 512 + threadIdx.x; rcnt && k < nrcnt; k += (long)gridDim.x * 512) rcnt[k] = 0u;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) count_event(EV_LAYER_REPAIR);
   for (long vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    edge16_tile<EPI, ASC>(g, vb, nvb);
+    // (the tiles read g through a laundered kernarg pointer: otherwise the compiler keeps the argument block in
+    // SGPRs across the loop and spills them, 91 SGPRs and 18 VGPRs against 0 and 11)
+    typedef const __attribute__((address_space(4))) char* kptr;
+    kptr kp = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    edge16_tile<EPI, ASC>(*(const EdgeArgs*)(const __attribute__((address_space(4))) EdgeArgs*)kp, vb, nvb);
     __syncthreads();
   }
 }
@@ -1224,10 +940,10 @@ constexpr int P_QP = 520;
 constexpr int P_QROWS = LDS_B / (P_QP * 4);  // 78 node rows
 }  // namespace
 
-// one pair tile: bid = pair tile * 2 + column tile (tid_in: the persistent kernel's opaque copy of threadIdx.x)
-__device__ __forceinline__ void pair_tile(const EdgeArgs& g, long bid, int tid_in) {
+// one pair tile: bid = pair tile * 2 + column tile
+__device__ __forceinline__ void pair_tile(const EdgeArgs& g, long bid) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = tid_in, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;  // rows 32 wm, columns 128 wn of the tile
   const int l16 = lane & 15, g4 = lane >> 4;
   const int n0 = (int)(bid & 1) * BN;
@@ -1425,7 +1141,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16_pairs_repair(EdgeArgs g, long
   for (long k = (long)blockIdx.x * 512 + threadIdx.x; k < nmax; k += (long)gridDim.x * 512) agg_max[k] = 0u;
   for (long k = (long)blockIdx.x * 512 + threadIdx.x; k < nrcnt; k += (long)gridDim.x * 512) rcnt[k] = 0u;
   for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    pair_tile(g, t, threadIdx.x);
+    pair_tile(g, t);
     __syncthreads();
   }
 }
@@ -1433,7 +1149,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16_pairs_repair(EdgeArgs g, long
 // edge layer 1 on pairs as a launch of its own (the two-launch schedule; the pair grid's repairs use
 // k_edge16_pairs_repair)
 __global__ __launch_bounds__(512, 1) void k_edge16_pairs(EdgeArgs g) {
-  pair_tile(g, remap(blockIdx.x, gridDim.x), threadIdx.x);
+  pair_tile(g, remap(blockIdx.x, gridDim.x));
 }
 
 hipError_t edge_gemm16_pairs(const EdgeArgs& g, hipStream_t s) {
@@ -1448,8 +1164,7 @@ hipError_t edge_gemm16_pairs(const EdgeArgs& g, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------
 // Both edge layers of a CSP layer in one grid, edge layer 1 on pairs (chm_internal.h PairSched).
-// The directed one-grid kernels (k_edge16_layer*) pair layer-1 row tile t with layer-2 row tile t; on pairs,
-// layer-2 row tile t reads the S rows of every pair tile of its crystals up to its last node's pair row, a
+// Layer-2 row tile t reads the S rows of every pair tile of its crystals up to its last node's pair row, a
 // contiguous range [lo(t), hi(t)] (pair_plan). Each XCD runs a contiguous range of row tiles and all the pair
 // tiles they read, so every S row a layer-2 tile reads was written through the same XCD's L2 (list x = the
 // jobs of one XCD). Ranges of neighbouring lists may share a pair tile: both compute it and write identical bytes.
@@ -1552,7 +1267,7 @@ __global__ __launch_bounds__(512, 1) void k_edge16_pairs_grid(EdgeArgs g1, EdgeA
     }
   };
   if (j.x == 1) {
-    pair_tile(g1, j.y, threadIdx.x);
+    pair_tile(g1, j.y);
     // every store of this tile has reached the XCD's L2; count the column tile (and a misplaced block)
     // (dbg 4194304, profiling: published without waiting for the stores, the drain's cost; wrong results)
     if (!(g1.dbg & 4194304)) {
@@ -1608,14 +1323,12 @@ static bool l2_uniform_ok(const EdgeArgs& g) {
          g.wscale && !g.rt_first && !g.rt_count && !g.rt_h && !g.rt_e0 &&
          (!g.rtiles || (g.sbuf && g.msgbuf && g.rcnt && (long)g.ntiles * BM >= g.E));
 }
-// The repair pair behind a one-grid launch (both exit at once unless the grid raised its repair request): the
-// launcher's own first repair kernel on repair_dim() blocks, then repair_layer2 recomputes every layer-2 tile of r2
-// without intra-grid waits, counted as event ev.
+// The pair grid's repair launches run on repair_dim() blocks (both exit at once unless the grid raised its repair
+// request); the second one recomputes every layer-2 tile of r2 without intra-grid waits.
 static dim3 repair_dim(int repair_grid) { return dim3((unsigned)(repair_grid > 0 ? repair_grid : 256)); }
-static hipError_t repair_layer2(const EdgeArgs& r2, int repair_grid, int ev, hipStream_t s) {
+static hipError_t repair_layer2(const EdgeArgs& r2, int repair_grid, hipStream_t s) {
   const long nb2 = (long)r2.ntiles * r2.npairs * (r2.N / BN);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), repair_dim(repair_grid), dim3(512), LDS_B, s, r2, nb2,
-                     (unsigned*)nullptr, 0L, (unsigned*)nullptr, 0L, ev);
+  hipLaunchKernelGGL((k_edge16_repair<EPI_SEGMEAN, true>), repair_dim(repair_grid), dim3(512), LDS_B, s, r2, nb2);
   return hipGetLastError();
 }
 
@@ -1624,7 +1337,7 @@ hipError_t edge_gemm16_pairs_layer(const EdgeArgs& g1, const EdgeArgs& g2, const
   if (g1.N != H || g1.K != FD || !g1.A || !g1.W || !g1.wscale || !g1.S || !g1.sexp || !g1.PQ || !g1.pi || !g1.pj ||
       !g1.pe || g1.Mp < 1 || g1.npairs != g2.npairs || g1.E < g1.Mp || !g1.xbad || g1.xbad != g2.xbad)
     return hipErrorInvalidValue;
-  if (!l2_uniform_ok(g2) || !g2.rtiles || g2.flags || g2.lflags || (long)g2.ntiles != ps.R)
+  if (!l2_uniform_ok(g2) || !g2.rtiles || (long)g2.ntiles != ps.R)
     return hipErrorInvalidValue;  // (uniform 256-row tiles only)
   if (!ps.jobs || !ps.pflag || ps.jstride < 1 || ps.npx < 1) return hipErrorInvalidValue;
   if (hipError_t e = edge16_init(); e != hipSuccess) return e;
@@ -1637,14 +1350,13 @@ hipError_t edge_gemm16_pairs_layer(const EdgeArgs& g1, const EdgeArgs& g2, const
   const long nb1 = (g1.Mp + PBM - 1) / PBM * (H / BN);
   hipLaunchKernelGGL(k_edge16_pairs_repair, repair_dim(repair_grid), dim3(512), LDS_B, s, g1, nb1, g2.agg_max,
                      g2.agg_max ? (long)g2.npairs * g2.nnodes : 0L, g2.rcnt, g2.rcnt ? (long)g2.npairs * g2.ntiles * 8 : 0L);
-  return repair_layer2(g2, repair_grid, EV_LAYER_REPAIR, s);
+  return repair_layer2(g2, repair_grid, s);
 }
 
 static hipError_t edge16_init_once() {
   const void* ks[] = {(const void*)k_edge16<EPI_STD, false>, (const void*)k_edge16<EPI_EDGE, false>,
                       (const void*)k_edge16<EPI_SEGMEAN, true>, (const void*)k_edge16<EPI_STD, true>,
-                      (const void*)k_edge16_tail, (const void*)k_edge16_layer, (const void*)k_edge16_layer_dyn,
-                      (const void*)k_edge16_repair<EPI_EDGE, false>, (const void*)k_edge16_repair<EPI_SEGMEAN, true>,
+                      (const void*)k_edge16_repair<EPI_SEGMEAN, true>,
                       (const void*)k_edge16_pairs, (const void*)k_edge16_pairs_grid, (const void*)k_edge16_pairs_repair,
                       (const void*)k_edge16_short};
   for (const void* k : ks) {
@@ -1668,83 +1380,6 @@ hipError_t edge_events_read(unsigned long long* out) {
 hipError_t edge_events_reset() {
   static const unsigned long long zero[EV_COUNT] = {};
   return hipMemcpyToSymbol(HIP_SYMBOL(g_edge_events), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-}
-
-hipError_t edge_gemm16_tail(const EdgeArgs& g1, const EdgeArgs& g2, int repair_grid, hipStream_t s) {
-  if (g1.N != H || g1.K % (2 * BK) || g1.aexp || !g1.S || !g1.sexp || !g1.PQ || !g1.node_off || !g1.natoms ||
-      !g1.n2g || !g1.A || !g1.W || !g1.wscale || g1.npairs > 2 || g1.M <= g1.row_base || g1.row_base < 0 ||
-      !g1.flags || g1.flags != g2.flags || g1.flag_row0 != g1.row_base || g2.flag_row0 != g1.row_base ||
-      !g2.xbad)
-    return hipErrorInvalidValue;
-  if (!l2_uniform_ok(g2) || !g2.tiles || g2.ntiles < 1) return hipErrorInvalidValue;  // (uniform tiles only)
-  if (hipError_t e = edge16_init(); e != hipSuccess) return e;
-  const long nt1 = ((g1.M - g1.row_base + BM - 1) / BM) * (g1.N / BN);
-  const long nb1 = (nt1 + 7) / 8 * 8;
-  const long nt2 = (long)g2.ntiles * g2.npairs * (g2.N / BN);
-  hipLaunchKernelGGL(k_edge16_tail, dim3((unsigned)(nb1 + nt2)), dim3(512), LDS_B, s, g1, g2, (int)nb1, (int)nt1);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || (g2.dbg & 16384)) return e;
-  // the repair pair (exits at once unless a segment tile's wait timed out): the first clears layer 2's
-  // agg row maxima (the failed tiles may have max-ed garbage; S itself was complete when the grid
-  // ended), the second recomputes every segment tile of edge layer 2 without intra-grid waits
-  EdgeArgs r1 = g1, r2 = g2;
-  r1.flags = r2.flags = nullptr;
-  r1.xbad = g2.xbad;
-  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), repair_dim(repair_grid), dim3(512), LDS_B, s, r1, 0L,
-                     g2.agg_max, g2.agg_max ? (long)g2.npairs * g2.nnodes : 0L, (unsigned*)nullptr, 0L, -1);
-  return repair_layer2(r2, repair_grid, EV_TAIL_REPAIR, s);
-}
-
-long edge16_layer_blocks(long R, int P) { return 8 * ((R + 7) / 8) * (2 + 2L * P); }
-
-// (host) the job of every block of a k_edge16_layer grid: out[2 b] = kind, out[2 b + 1] = tile index
-void edge16_layer_jobs(long R, int P, int D, long* out) {
-  const long nb = edge16_layer_blocks(R, P);
-  for (long b = 0; b < nb; ++b) {
-    const LayerJob j = layer_job(b, R, P, D);
-    out[2 * b] = j.kind;
-    out[2 * b + 1] = j.bid;
-  }
-}
-
-void edge16_seq_jobs(long n, int P, int D, long* out) {
-  for (long k = 0; k < n; ++k) {
-    const SeqJob j = seq_job(k, P, D);
-    out[3 * k] = j.kind;
-    out[3 * k + 1] = j.row;
-    out[3 * k + 2] = j.sub;
-  }
-}
-
-hipError_t edge_gemm16_layer(const EdgeArgs& g1, const EdgeArgs& g2, int lag, int repair_grid, hipStream_t s,
-                             unsigned* sched, int cap, int grid, int pool, int skip_xcd) {
-  if (g1.N != H || g1.K % (2 * BK) || g1.aexp || !g1.S || !g1.sexp || !g1.PQ || !g1.node_off || !g1.natoms ||
-      !g1.n2g || !g1.A || !g1.W || !g1.wscale || g1.npairs > 2 || g1.row_base != 0 || g1.flags || !g1.lflags ||
-      !g1.xbad || g1.xbad != g2.xbad)
-    return hipErrorInvalidValue;
-  if (!l2_uniform_ok(g2) || !g2.rtiles || g2.flags || g2.lflags != g1.lflags || g2.npairs != g1.npairs ||
-      (long)g2.ntiles * BM - g2.E >= BM || g1.M != g1.E || lag < 1)
-    return hipErrorInvalidValue;  // (uniform 256-row tiles only)
-  if (hipError_t e = edge16_init(); e != hipSuccess) return e;
-  const long R = g2.ntiles;
-  if (sched) {  // persistent, the last rows claimed at run time (k_edge16_layer_dyn)
-    if (grid < 1 || cap < R + lag + 64 || pool < 0 || pool > 100) return hipErrorInvalidValue;
-    const int ns = (int)((R - (R * pool + 99) / 100) / 8);  // static rows per XCD
-    hipLaunchKernelGGL(k_edge16_layer_dyn, dim3((unsigned)grid), dim3(512), LDS_B, s, g1, g2, (int)R, lag, sched, cap,
-                       ns, skip_xcd);
-  } else {
-    const long blocks = edge16_layer_blocks(R, g2.npairs);
-    hipLaunchKernelGGL(k_edge16_layer, dim3((unsigned)blocks), dim3(512), LDS_B, s, g1, g2, (int)R, lag);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || (g1.dbg & 16384)) return e;  // (dbg 16384: profiling / tests, no repair launches)
-  // the repair pair (exits at once unless a layer-2 tile flagged another XCD's layer-1 tile)
-  EdgeArgs r1 = g1, r2 = g2;
-  r1.lflags = r2.lflags = nullptr;
-  const long nb1 = ((g1.M + BM - 1) / BM) * (g1.N / BN);
-  hipLaunchKernelGGL((k_edge16_repair<EPI_EDGE, false>), repair_dim(repair_grid), dim3(512), LDS_B, s, r1, nb1,
-                     g2.agg_max, (long)g2.npairs * g2.nnodes, g1.lflags, R, -1, g2.rcnt, (long)g2.npairs * R * 8);
-  return repair_layer2(r2, repair_grid, EV_LAYER_REPAIR, s);
 }
 
 hipError_t edge_gemm16(const EdgeArgs& g, int epi, hipStream_t s) {

@@ -62,22 +62,16 @@ struct Option {
 using M = chm_model;
 const Option kOptions[] = {
     {"node_ps", "CHM_NODE_PS", &M::node_ps, FLAG},
-    {"edge_split", "CHM_EDGE_SPLIT", &M::edge_split, FLAG},
     {"edge_rows", "CHM_EDGE_ROWS", &M::edge_rows, FLAG},
     {"edge_layer", "CHM_EDGE_LAYER", &M::edge_layer, FLAG},
     {"edge_pairs", "CHM_EDGE_PAIRS", &M::edge_pairs, FLAG},
     {"edge_pairs_layer", "CHM_EDGE_PAIRS_LAYER", &M::edge_pairs_layer, FLAG},
     {"edge_rows_short", "CHM_EDGE_ROWS_SHORT", &M::edge_rows_short, FLAG},
-    {"edge_layer_dyn", "CHM_EDGE_DYN", &M::edge_dyn, INT, 0, 2, "edge_layer_dyn must be 0, 1 or 2"},
-    {"edge_pool", "CHM_EDGE_POOL", &M::edge_pool, INT, 0, 100, "edge_pool must be in [0, 100]"},
     {"edge_lag", "CHM_EDGE_LAG", &M::edge_lag, INT, 1, kMaxLag, "edge_lag must be in [1, 1000]"},
     {"edge_layer_min", "CHM_EDGE_LAYER_MIN", &M::edge_layer_min, INT, 1, INT64_MAX, "edge_layer_min must be >= 1"},
-    {"edge_dyn_skip_xcd", nullptr, &M::edge_skip_xcd, INT, -1, 7, "edge_dyn_skip_xcd must be in [-1, 7]"},
     {"xcd_mask", nullptr, &M::xcd_mask, INT},
     {"edge_rows_nowait", nullptr, &M::edge_dbg, BIT, 64},
     {"edge_layer_repair", nullptr, &M::edge_dbg, BIT, 512},
-    {"edge_tail_timeout", nullptr, &M::edge_dbg, BIT, 8192},
-    {"edge_tail_norepair", nullptr, &M::edge_dbg, BIT, 16384},
     {"edge_pairs_pq_global", nullptr, &M::edge_dbg, BIT, 1048576},
     {nullptr, "CHM_EDGE_DBG", &M::edge_dbg, INT},
     {nullptr, "CHM_NODE_GLDS", &M::node_glds, INT},
@@ -219,8 +213,8 @@ extern "C" int chm_model_create(const chm_dims* dims, const float* const* p, int
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&m->ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       m->ncu = 0;
     m->device = dev;
-    // k_edge16_layer_dyn gives each of 8 XCDs static rows: on a device or partition mode with fewer XCDs
-    // it would leave rows to its self-check and repair launches, so it runs only where 8 were seen
+    // the pair grid gives each of 8 XCDs a job list of its own: on a device or partition mode with fewer XCDs every
+    // launch would end in its repair launches, so it runs only where 8 were seen
     if (m->ncu > 0 && xcd_mask(8 * m->ncu, &m->xcd_mask) != hipSuccess) m->xcd_mask = 0;
     struct Job { const float* src; size_t n; const void** dst; };
     std::vector<Job> jobs;

@@ -216,7 +216,7 @@ class CSPNet(nn.Module):
             return self._hip
 
     def set_option(self, key: str, value: int):
-        """Launch-schedule option of the C ABI (chm_model_set_option, e.g. 'edge_split'); results are
+        """Launch-schedule option of the C ABI (chm_model_set_option, e.g. 'edge_layer'); results are
         bit-identical either way. Survives rebuilds of the packed weights."""
         with self._hip_lock:
             _lib.check(_lib.load().chm_model_set_option(self.hip_model().handle, key.encode(), int(value)),

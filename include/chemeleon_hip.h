@@ -81,10 +81,8 @@ int chm_model_create(const chm_dims* dims, const float* const* d_params, int n_p
 void chm_model_destroy(chm_model* m);
 
 /* Launch-schedule options (not thread-safe against concurrent steps of the same model):
- *   "edge_split" (0 / 1): when edge layer 1's 256x256 tiles leave a partial last round of the
- *     grid, run that round in one grid with the edge-layer-2 tiles that do not read its rows.
  *   "edge16" (1): accepted for compatibility (the round-1 32x32x16 kernels were removed; 0 fails).
- *   "edge_rows", "edge_layer", "edge_layer_dyn", "edge_pool", "edge_lag", "edge_layer_min": edge-layer
+ *   "edge_rows", "edge_layer", "edge_lag", "edge_layer_min", "edge_rows_short": edge-layer
  *     schedules (bit-identical). A batch plans its pair-grid job lists (and sizes their
  *     buffers) with the edge_lag of its creation: a later change reaches batches created after it only.
  *   "node_ps" (0 / 1): split16 node GEMMs read their A operands pre-split by the producing kernels (not
@@ -95,11 +93,9 @@ void chm_model_destroy(chm_model* m);
  *     from one GEMM row; within fp32 rounding of the directed form (DESIGN.md §4 "Edge layer 1 on pairs").
  *   "edge_pairs_layer" (0 / 1, default 1): with edge_pairs, both edge layers in one static grid from
  *     "edge_layer_min" row tiles on (k_edge16_pairs_grid; bit-identical to two launches).
- *   The persistent one-grid kernel (edge_layer_dyn) runs only where model creation saw 8 XCDs ("xcd_mask" =
- *     0xff); tests: "edge_dyn_skip_xcd" (its blocks on one XCD exit, the launch's self-check must raise the
- *     repair), "edge_layer_repair", "edge_tail_timeout", "edge_tail_norepair" (WRONG results after a
- *     timeout), "edge_rows_nowait", "edge_pairs_pq_global" (the pair epilogue's P / Q rows from global memory
- *     instead of LDS).
+ *   The one-grid schedule runs only where model creation saw 8 XCDs ("xcd_mask" = 0xff); tests:
+ *     "edge_layer_repair" (its layer-2 jobs always request the repair launches), "edge_rows_nowait",
+ *     "edge_pairs_pq_global" (the pair epilogue's P / Q rows from global memory instead of LDS).
  * Returns CHM_E_ARG for an unknown key. */
 int chm_model_set_option(chm_model* m, const char* key, int64_t value);
 
@@ -576,18 +572,6 @@ int chm_debug_row_nodes_ex(const int32_t* h_natoms, int B, int64_t nbig, int32_t
                            int64_t cap);
 int64_t chm_debug_short_row_tiles(const int32_t* h_natoms, int B, int P, int ncu, int64_t layer_min);
 int64_t chm_batch_short_row_tiles(const chm_batch* b);
-/* Host-only test hook: the block -> job map of the one-grid edge-layer kernel (k_edge16_layer) for R
- * row tiles, P conditionings and layer-2 lag `lag`. Returns the grid size nb (or a negative CHM_E_*);
- * if out holds >= 2 nb int64 it receives per block {kind (0 none, 1 edge layer 1, 2 edge layer 2),
- * tile index (layer 1: row tile * 2 + column tile; layer 2: (row tile * P + conditioning) * 2 +
- * column tile)}. */
-int64_t chm_debug_layer_jobs(int64_t R, int P, int lag, int64_t* out, int64_t cap);
-/* The persistent form of that kernel (option edge_layer_dyn, the default from 1024 row tiles on): job k
- * of an XCD's sequence as out[3k] = kind (1 = layer 1, 2 = layer 2), out[3k+1] = the XCD's local row
- * (the first ones its static rows, the rest claimed from the shared pool at run time), out[3k+2] =
- * column tile (layer 1) or conditioning * 2 + column tile (layer 2), for k < n. */
-int chm_debug_layer_seq(int64_t n, int P, int lag, int64_t* out);
-
 /* Host-only test hook: the schedule of both edge layers in one static grid on pairs (k_edge16_pairs_grid; block
  * 8 k + x runs job k of list x) for an fc batch of these crystals, P conditionings and lag `lag` (pair tiles).
  * Returns the job-list stride J (or a negative CHM_E_*); when the buffers are large enough: rng [2 R] = per
@@ -619,7 +603,7 @@ int chm_edge_features_split(chm_batch* b, const float* d_frac, void* d_split, vo
  *   CHM_K_EDGE_MESSAGE  edge layer 2 (message GEMM + SiLU)
  *   CHM_K_SEGMENT_MEAN  message-passing aggregation (scatter_mean)
  *   CHM_K_DECODER       one whole decoder call (all its kernels)
- *   CHM_K_EDGE_LAYER    both edge layers of a CSP layer in one grid (k_edge16_layer + its repair pair) */
+ *   CHM_K_EDGE_LAYER    both edge layers of a CSP layer in one grid (k_edge16_pairs_grid + its repair pair) */
 #define CHM_K_EDGE_FOURIER 0
 #define CHM_K_EDGE_MESSAGE 1
 #define CHM_K_SEGMENT_MEAN 2
@@ -630,13 +614,11 @@ int chm_prof_reset(void);
 int chm_prof_read(int kernel, int64_t* launches, double* total_ms);
 /* Health counters of the edge kernels, counted on the device over every launch and graph replay
  * since the last chm_prof_events_reset (synchronous device reads; not while capturing):
- *   out[CHM_EV_LAYER_TIMEOUT]  k_edge16_layer: layer-2 tiles whose wait for their layer-1 tiles timed out
- *   out[CHM_EV_LAYER_XCD]      k_edge16_layer: layer-2 tiles whose layer-1 tiles ran on another XCD
- *   out[CHM_EV_LAYER_REPAIR]   k_edge16_layer launches recomputed by their repair pair
- *   out[CHM_EV_TAIL_TIMEOUT]   k_edge16_tail: segment tiles whose wait for this grid's layer-1 tiles timed out
- *   out[CHM_EV_TAIL_REPAIR]    k_edge16_tail launches whose edge layer 2 was recomputed
- *   out[CHM_EV_LAYER_INCOMPLETE] k_edge16_layer_dyn launches that ended with layer-2 tiles not computed (an
- *                              XCD missing: the persistent kernel's static rows assume 8 XCDs; repaired)
+ *   out[CHM_EV_LAYER_TIMEOUT]  pair grid: layer-2 jobs whose wait for their pair tiles timed out
+ *   out[CHM_EV_LAYER_XCD]      pair grid: layer-2 jobs whose pair tiles ran on another XCD
+ *   out[CHM_EV_LAYER_REPAIR]   pair-grid launches recomputed by their repair pair
+ *   out[CHM_EV_TAIL_TIMEOUT], out[CHM_EV_TAIL_REPAIR], out[CHM_EV_LAYER_INCOMPLETE]: reserved, always 0 (they
+ *                              counted the tail grid and the persistent one-grid kernel, both removed)
  * Results never depend on these (a raised check is repaired before the layer's output is used); a
  * non-zero count means the run paid for the repairs. n <= 8 values are written. */
 #define CHM_EV_LAYER_TIMEOUT 0

@@ -191,16 +191,16 @@ def test_segment_mean_refuses_mis_sized_messages():
 # chm_model_set_option's whole surface: key -> None (every int64 is taken) or (lowest, highest, refusal text)
 _I64 = (-2**63, 2**63 - 1)
 OPTIONS = {
-    "node_ps": None, "edge_split": None, "edge_rows": None, "edge_layer": None, "edge_pairs": None,
+    "node_ps": None, "edge_rows": None, "edge_layer": None, "edge_pairs": None,
     "edge_pairs_layer": None, "edge_rows_short": None, "xcd_mask": None,
-    "edge_layer_repair": None, "edge_tail_timeout": None, "edge_tail_norepair": None, "edge_pairs_pq_global": None,
+    "edge_layer_repair": None, "edge_pairs_pq_global": None,
     "edge_rows_nowait": None,
-    "edge_layer_dyn": (0, 2, b"edge_layer_dyn must be 0, 1 or 2"),
-    "edge_dyn_skip_xcd": (-1, 7, b"edge_dyn_skip_xcd must be in [-1, 7]"),
     "edge_layer_min": (1, _I64[1], b"edge_layer_min must be >= 1"),
-    "edge_pool": (0, 100, b"edge_pool must be in [0, 100]"),
     "edge_lag": (1, 1000, b"edge_lag must be in [1, 1000]"),
 }
+# keys of the directed one-grid and tail-grid schedules, removed with them
+RETIRED_OPTIONS = ("edge_split", "edge_layer_dyn", "edge_pool", "edge_dyn_skip_xcd", "edge_tail_timeout",
+                   "edge_tail_norepair")
 
 
 @pytest.mark.gpu
@@ -228,6 +228,18 @@ def test_model_options_accept_their_ranges_and_refuse_the_rest():
     assert set_option("edge_lagg", 1) == -1
     assert lib.chm_last_error() == b"unknown option: edge_lagg"
     assert lib.chm_model_set_option(h, None, 1) == -1 and lib.chm_model_set_option(None, b"edge_lag", 1) == -1
+
+
+@pytest.mark.gpu
+def test_retired_model_options_are_unknown():
+    """The option keys of the removed edge schedules are refused like any unknown key, whatever the value."""
+    m, _b = _gpu_batch([2], 1)
+    lib = _lib.load()
+    h = m.decoder.hip_model().handle
+    for key in RETIRED_OPTIONS:
+        for v in (0, 1):
+            assert lib.chm_model_set_option(h, key.encode(), v) == -1, (key, v)
+            assert lib.chm_last_error() == b"unknown option: " + key.encode(), (key, lib.chm_last_error())
 
 
 @pytest.mark.gpu

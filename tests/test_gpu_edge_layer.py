@@ -41,7 +41,7 @@ SENT = -12345.6787109375  # d_agg's pre-fill (exact in fp32)
 MATHS = ["split16", "bf16x3", "f32"]
 # every launch-schedule option these tests touch, at the model's defaults
 DEFAULTS = dict(edge_pairs=1, edge_pairs_layer=1, edge_rows=1, edge_rows_nowait=0, edge_rows_short=1, edge_layer=1,
-                edge_lag=8, edge_layer_dyn=1, edge_layer_min=256, edge_split=1, node_ps=0)
+                edge_lag=8, edge_layer_min=256, node_ps=0)
 
 
 def _decoder(sd):
@@ -173,16 +173,10 @@ def test_accuracy_coincident_atoms_and_cell_edges(dec, math, shape):
 # repairs and timeouts. edge_layer_min 1 engages the one-grid forms at these sizes; short: the batch must (True) or
 # must not (False) take 192-row tiles; grid: launches of the one-grid kernels (CHM_K_EDGE_LAYER) the call must record.
 DIRECTED = [
-    ("node-aligned segment tiles", dict(edge_pairs=0, edge_rows=0, edge_layer=0, edge_split=0), False, 0),
+    ("node-aligned segment tiles", dict(edge_pairs=0, edge_rows=0, edge_layer=0), False, 0),
     ("row tiles", dict(edge_pairs=0, edge_rows=1, edge_layer=0, edge_rows_short=0), False, 0),
     ("row tiles, msgbuf path", dict(edge_pairs=0, edge_rows=1, edge_rows_nowait=1, edge_layer=0, edge_rows_short=0), False, 0),
     ("short row tiles", dict(edge_pairs=0, edge_rows=1, edge_layer=0, edge_rows_short=1), True, 0),
-    ("one grid, persistent, lag 10", dict(edge_pairs=0, edge_layer=1, edge_lag=10, edge_layer_dyn=2, edge_layer_min=1), False, 1),
-    ("one grid, persistent, lag 1", dict(edge_pairs=0, edge_layer=1, edge_lag=1, edge_layer_dyn=2, edge_layer_min=1), False, 1),
-    ("one grid, static map, lag 10", dict(edge_pairs=0, edge_layer=1, edge_lag=10, edge_layer_dyn=0, edge_layer_min=1), False, 1),
-    ("one grid, static map, lag 1", dict(edge_pairs=0, edge_layer=1, edge_lag=1, edge_layer_dyn=0, edge_layer_min=1), False, 1),
-    ("one grid, lag 10, msgbuf path", dict(edge_pairs=0, edge_layer=1, edge_lag=10, edge_layer_dyn=2, edge_layer_min=1,
-                                           edge_rows_nowait=1), False, 1),
 ]
 PAIRS = [
     ("pairs, two launches, row tiles", dict(edge_pairs=1, edge_pairs_layer=0, edge_rows_short=0), False, 0),
@@ -229,17 +223,6 @@ def test_schedules(dec, group, shape, pairs):
     finally:
         lib.chm_prof_enable(0)
         lib.chm_prof_reset()
-
-
-def test_tail_split_needs_more_tiles_than_these_shapes_have():
-    """Option edge_split (k_edge16_tail): taken only when edge layer 1 has more 256x256 tiles than the device has CUs
-    and a short partial round; no option lowers that threshold."""
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    tiles1 = max((sum(n * n for n in nat) + 255) // 256 * (H // 256) for nat in EC.SHAPES.values())
-    if tiles1 <= ncu:
-        pytest.skip(f"edge_split: the largest shape here has {tiles1} layer-1 tiles on {ncu} CUs, the tail grid needs more "
-                    "tiles than CUs and no option lowers that; test_edge_tail_split_is_bit_identical covers it")
-    pytest.fail("a device this small takes the tail split at these shapes: add it to DIRECTED")
 
 
 # ---------------------------------------------------------------- exactness

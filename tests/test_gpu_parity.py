@@ -306,74 +306,6 @@ def test_t1_step_512x40_math(model1000, golden, cn, math):
           f"{', '.join(f'atom {i} {rg[i]:.1e}' for i in np.argsort(rg)[:3])}")
 
 
-@pytest.mark.parametrize("nat", [[40] * 64, [50] * 40, [23, 7, 40, 1, 80] * 23])
-def test_edge_tail_split_is_bit_identical(cn, nat):
-    """When edge layer 1's 256x256 tiles leave a short partial round of the grid (64 x 40: 800 tiles
-    on 256 CUs), the runtime runs that round in one grid with edge layer 2, whose segment tiles that
-    read its rows wait for them inside the grid (decoder.hip edge_block, option 'edge_split';
-    k_edge16_tail). Same tiles, same arithmetic: one reverse step must agree bit for bit with the
-    one-launch-per-layer schedule. Shapes: partial rounds of 32, 14 and 6 tiles (ragged: segment
-    tiles spanning crystals of 1-80 atoms wait on layer-1 tiles)."""
-    B, N = len(nat), sum(nat)
-    g = torch.Generator().manual_seed(11)
-    a0 = torch.randint(0, 100, (N,), generator=g)
-    x0 = torch.rand(N, 3, generator=g)
-    l0 = torch.eye(3).expand(B, 3, 3) * 4.0 + 0.3 * torch.randn(B, 3, 3, generator=g)
-    nz = (torch.rand((N, 104), generator=g), torch.randn(B, 3, 3, generator=g), torch.randn(N, 3, generator=g),
-          torch.randn(N, 3, generator=g))
-    model = _model(1000)  # its own instance: the option stays out of the shared fixtures
-    model.decoder.set_option("edge_pairs", 0)  # (the directed edge-layer-1 schedules under test)
-    outs = []
-    for split in (1, 0):
-        model.decoder.set_option("edge_split", split)
-        outs.append([o.cpu() for o in model.reverse_step(500, a0, x0, l0, nat, 2.0, 1e-5, cn[0], cn[1], noise=nz)])
-    del model
-    torch.cuda.empty_cache()
-    for u, v, what in zip(outs[0], outs[1], ("types", "frac", "lattice")):
-        assert torch.equal(u, v), f"{what}: split and one-launch-per-layer edge schedules differ"
-
-
-def test_edge_tail_timeout_is_flagged_and_repaired(cn):
-    """k_edge16_tail's bounded waits (a segment tile reading rows of the grid's own layer-1 tiles) never
-    give a silent wrong answer: with the layer-1 tiles delayed ~10 ms and the waits shortened (option
-    'edge_tail_timeout'), the waits time out, the tiles raise the repair flag, the repair launches
-    recompute edge layer 2, and the step equals the one-launch-per-layer schedule bit for bit. The
-    device counters see the timeouts and repairs; without the repair ('edge_tail_norepair') the same
-    run gives different numbers, so the forced timeout really read unwritten S."""
-    nat = [40] * 64  # layer 1: 800 tiles on 256 CUs, a partial round of 32 -> the tail grid
-    B, N = len(nat), sum(nat)
-    g = torch.Generator().manual_seed(13)
-    a0 = torch.randint(0, 100, (N,), generator=g)
-    x0 = torch.rand(N, 3, generator=g)
-    l0 = torch.eye(3).expand(B, 3, 3) * 4.0 + 0.3 * torch.randn(B, 3, 3, generator=g)
-    nz = (torch.rand((N, 104), generator=g), torch.randn(B, 3, 3, generator=g), torch.randn(N, 3, generator=g),
-          torch.randn(N, 3, generator=g))
-    model = _model(1000)
-    model.decoder.set_option("edge_pairs", 0)  # (the directed edge-layer-1 schedules under test)
-    model.decoder.set_option("edge_layer", 0)  # (the one-grid kernel would take this shape)
-    outs, events = [], []
-    for split, timeout, norepair in ((0, 0, 0), (1, 0, 0), (1, 1, 0), (1, 1, 1)):
-        model.decoder.set_option("edge_split", split)
-        model.decoder.set_option("edge_tail_timeout", timeout)
-        model.decoder.set_option("edge_tail_norepair", norepair)
-        _lib.prof_events(reset=True)
-        outs.append([o.cpu() for o in model.reverse_step(500, a0, x0, l0, nat, 2.0, 1e-5, cn[0], cn[1], noise=nz)])
-        torch.cuda.synchronize()
-        events.append(_lib.prof_events())
-    del model
-    torch.cuda.empty_cache()
-    print("events (two launches, tail, forced timeout, forced timeout without repair):", events)
-    assert events[0]["tail_wait_timeouts"] == 0 and events[1]["tail_wait_timeouts"] == 0
-    assert events[1]["tail_repairs"] == 0
-    assert events[2]["tail_wait_timeouts"] > 0 and events[2]["tail_repairs"] > 0
-    assert events[3]["tail_wait_timeouts"] > 0 and events[3]["tail_repairs"] == 0
-    for k, name in ((1, "tail grid"), (2, "tail grid, timed out + repaired")):
-        for u, v, what in zip(outs[0], outs[k], ("types", "frac", "lattice")):
-            assert torch.equal(u, v), f"{what}: {name} differs from one launch per layer"
-    assert not all(torch.equal(u, v) for u, v in zip(outs[0][1:], outs[3][1:])), \
-        "the forced timeout did not change the unrepaired result (the test would not see a missing repair)"
-
-
 @pytest.mark.parametrize("nat", [[40] * 64, [20] * 48, [80] * 9, [1] * 300 + [2] * 70 + [3] * 9,
                                  [23, 7, 40, 1, 80] * 23, [5, 9, 3, 12, 7, 1, 20]])
 def test_edge_row_tiles_are_bit_identical(cn, nat):
@@ -381,12 +313,9 @@ def test_edge_row_tiles_are_bit_identical(cn, nat):
     a tile end keeps one sequential sum over its edges (the previous tile publishes its partial sum,
     the next continues it, or finishes it from the continued rows left in msgbuf when the partial was
     not there in time). One reverse step must agree bit for bit with node-aligned segment tiles, with
-    the waiting path and with the msgbuf path forced ('edge_rows_nowait'). Shapes: 64 x 40 (with the
-    layer-1 tail split), crystals of 20 and 80 atoms, runs of 1-3-atom crystals (up to 256 nodes per
-    tile), ragged 1-80, a small mixed batch. The same for both edge layers in one grid (option
-    'edge_layer', k_edge16_layer: layer-2 row tiles wait for the layer-1 tiles of their rows and read S
-    through the XCD's L2) at lags of 10, 1 and 3 row tiles, and with its repair launches forced
-    ('edge_layer_repair': the layer recomputed on the two-launch schedule)."""
+    the waiting path and with the msgbuf path forced ('edge_rows_nowait'). Shapes: 64 x 40 (400 row tiles, above
+    'edge_layer_min': with 'edge_pairs' off the directed edge layers still run as two launches), crystals of 20
+    and 80 atoms, runs of 1-3-atom crystals (up to 256 nodes per tile), ragged 1-80, a small mixed batch."""
     B, N = len(nat), sum(nat)
     g = torch.Generator().manual_seed(12)
     a0 = torch.randint(0, 100, (N,), generator=g)
@@ -398,65 +327,18 @@ def test_edge_row_tiles_are_bit_identical(cn, nat):
     model.decoder.set_option("edge_pairs", 0)  # (the directed edge-layer-1 schedules under test)
     outs = []
     _lib.prof_events(reset=True)
-    for rows, nowait, layer, lag, repair, dyn in ((0, 0, 0, 10, 0, 2), (1, 0, 0, 10, 0, 2), (1, 1, 0, 10, 0, 2),
-                                                  (1, 0, 0, 10, 0, 2), (1, 0, 1, 10, 0, 2), (1, 0, 1, 1, 0, 2),
-                                                  (1, 1, 1, 3, 0, 2), (1, 0, 1, 10, 1, 2), (1, 0, 1, 10, 0, 0),
-                                                  (1, 0, 1, 2, 0, 0), (1, 0, 1, 10, 1, 0)):
+    for rows, nowait in ((0, 0), (1, 0), (1, 1), (1, 0)):
         model.decoder.set_option("edge_rows", rows)
         model.decoder.set_option("edge_rows_nowait", nowait)
-        model.decoder.set_option("edge_layer", layer)
-        model.decoder.set_option("edge_lag", lag)
-        model.decoder.set_option("edge_layer_repair", repair)
-        model.decoder.set_option("edge_layer_dyn", dyn)
         outs.append([o.cpu() for o in model.reverse_step(500, a0, x0, l0, nat, 2.0, 1e-5, cn[0], cn[1], noise=nz)])
     torch.cuda.synchronize()
     ev = _lib.prof_events()
     del model
     torch.cuda.empty_cache()
     assert ev["layer_wait_timeouts"] == 0 and ev["tail_wait_timeouts"] == 0, ev
-    for k, name in ((1, "row tiles"), (2, "row tiles, msgbuf path"), (3, "row tiles, second run"),
-                    (4, "both edge layers in one persistent grid"), (5, "one grid, lag 1"),
-                    (6, "one grid, lag 3, msgbuf path"), (7, "one grid + forced repair launches"),
-                    (8, "one grid, static block map"), (9, "one grid, static map, lag 2"),
-                    (10, "one grid, static map + forced repair")):
+    for k, name in ((1, "row tiles"), (2, "row tiles, msgbuf path"), (3, "row tiles, second run")):
         for u, v, what in zip(outs[0], outs[k], ("types", "frac", "lattice")):
             assert torch.equal(u, v), f"{what}: {name} differ from node-aligned segment tiles"
-
-
-@pytest.mark.parametrize("nat", [[40] * 64, [23, 7, 40, 1, 80] * 23])
-def test_persistent_edge_kernel_with_a_missing_xcd_is_repaired(cn, nat):
-    """k_edge16_layer_dyn hands each of the 8 XCDs static row tiles. On a device (or partition mode)
-    with fewer XCDs those rows would never run: the launch counts its finished layer-2 tiles, the last
-    block out raises the repair request when any are missing, and the repair launches recompute the
-    layer. Forced here by making the blocks on XCD 5 exit at once ('edge_dyn_skip_xcd'):
-    the step equals the static map's bit for bit and the device counters record the incomplete
-    launches and their repairs. Model creation also probes the XCDs and runs the persistent form only
-    where all 8 were seen ('xcd_mask')."""
-    B, N = len(nat), sum(nat)
-    g = torch.Generator().manual_seed(14)
-    a0 = torch.randint(0, 100, (N,), generator=g)
-    x0 = torch.rand(N, 3, generator=g)
-    l0 = torch.eye(3).expand(B, 3, 3) * 4.0 + 0.3 * torch.randn(B, 3, 3, generator=g)
-    nz = (torch.rand((N, 104), generator=g), torch.randn(B, 3, 3, generator=g), torch.randn(N, 3, generator=g),
-          torch.randn(N, 3, generator=g))
-    model = _model(1000)
-    model.decoder.set_option("edge_pairs", 0)  # (the directed edge-layer-1 schedules under test)
-    outs, events = [], []
-    for dyn, skip in ((0, -1), (2, -1), (2, 5)):
-        model.decoder.set_option("edge_layer_dyn", dyn)
-        model.decoder.set_option("edge_dyn_skip_xcd", skip)
-        _lib.prof_events(reset=True)
-        outs.append([o.cpu() for o in model.reverse_step(500, a0, x0, l0, nat, 2.0, 1e-5, cn[0], cn[1], noise=nz)])
-        torch.cuda.synchronize()
-        events.append(_lib.prof_events())
-    del model
-    torch.cuda.empty_cache()
-    print("events (static map, persistent, persistent without XCD 5):", events)
-    assert events[1]["layer_incomplete"] == 0 and events[1]["layer_repairs"] == 0
-    assert events[2]["layer_incomplete"] == 12 and events[2]["layer_repairs"] == 12  # 2 decoder pairs x 6 layers
-    for k in (1, 2):
-        for u, v, what in zip(outs[0], outs[k], ("types", "frac", "lattice")):
-            assert torch.equal(u, v), f"{what}: persistent kernel (variant {k}) differs from the static map"
 
 
 @pytest.mark.parametrize("nat", [[40] * 64, [23, 7, 40, 1, 80] * 23])
@@ -494,37 +376,6 @@ def test_presplit_node_gemms_match_in_loop_split(cn, nat):
     errs = [close(u, v, rtol=8e-6, what=w) for u, v, w in zip(decs[0], decs[1], ("node", "types", "coords", "lattice"))]
     print(f"pre-split vs in-loop split: step |dx| {dx:.2e}, lattice {dl:.2e}; decoder scaled errors "
           + ", ".join(f"{e:.1e}" for e in errs))
-
-
-def test_one_grid_edge_layers_single_conditioning(cn):
-    """k_edge16_layer with one conditioning (P = 1: a plain decoder call, as the CrystalClip graph
-    encoder and `CSPNet.forward` make): 64 x 40 (400 row tiles, above the one-grid threshold) and a
-    ragged batch, decoder outputs bit-identical to the two-launch schedule, also with the repair
-    launches forced."""
-    model = _model(1000)
-    model.decoder.set_option("edge_pairs", 0)  # (the directed edge-layer-1 schedules under test)
-    for nat in ([40] * 64, torch.randint(1, 81, (160,), generator=torch.Generator().manual_seed(5)).tolist()):
-        B, N = len(nat), sum(nat)
-        g = torch.Generator().manual_seed(21)
-        at = torch.randint(0, 100, (N,), generator=g).to(DEV)
-        fr = torch.rand(N, 3, generator=g).to(DEV)
-        la = (torch.eye(3).expand(B, 3, 3) * 4.0 + 0.3 * torch.randn(B, 3, 3, generator=g)).to(DEV)
-        te = model.time_embed(torch.full((B,), 300, dtype=torch.long)).to(DEV)
-        nat_t = torch.tensor(nat)
-        outs = []
-        for layer, repair, dyn in ((0, 0, 2), (1, 0, 2), (1, 1, 2), (1, 0, 0)):
-            model.decoder.set_option("edge_layer", layer)
-            model.decoder.set_option("edge_layer_repair", repair)
-            model.decoder.set_option("edge_layer_dyn", dyn)
-            o = model.decoder(atom_types=at, frac_coords=fr, lattices=la, num_atoms=nat_t.to(DEV),
-                              node2graph=torch.arange(B).repeat_interleave(nat_t).to(DEV), t=te,
-                              text_embeds=cn[0].expand(B, -1).to(DEV))
-            outs.append([o.node_features.cpu(), o.atom_types_out.cpu(), o.coords_out.cpu(), o.lattice_out.cpu()])
-        for k in (1, 2, 3):
-            for u, v in zip(outs[0], outs[k]):
-                assert torch.equal(u, v), f"one-grid (variant {k}) differs from two launches, P = 1, B = {B}"
-    del model
-    torch.cuda.empty_cache()
 
 
 @pytest.mark.timeout(300)

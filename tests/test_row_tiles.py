@@ -195,66 +195,3 @@ def test_short_row_tiles_choice(natoms, P, ncu, lmin, want):
         E = sum(n * n for n in natoms)
         R = got + (E - 256 * got + 191) // 192
         assert (R - got) * 2 * P <= ncu and 256 * got < E
-
-
-@pytest.mark.parametrize("R,P,lag", [(400, 2, 10), (3200, 2, 10), (1367, 1, 10), (256, 2, 1), (300, 2, 3),
-                                     (7, 2, 10), (9, 1, 4), (17500, 2, 10)])
-def test_layer_grid_schedule(R, P, lag):
-    """The one-grid edge-layer kernel's block -> job map (chm_debug_layer_jobs, the same function the
-    kernel runs): every layer-1 tile (row tile, column tile) and every layer-2 tile (row tile,
-    conditioning, column tile) is run by exactly one block, and every layer-2 block comes after both
-    layer-1 blocks of its rows in the same XCD's sequence (blockIdx = XCD + 8 k): the invariant that
-    keeps the in-grid waits free of deadlock (a waiting block's producers were dispatched before it)."""
-    lib = _lib.load()
-    nb = lib.chm_debug_layer_jobs(R, P, lag, None, 0)
-    assert nb > 0
-    out = (ctypes.c_int64 * (2 * nb))()
-    assert lib.chm_debug_layer_jobs(R, P, lag, out, 2 * nb) == nb
-    jobs = np.frombuffer(out, dtype=np.int64).reshape(nb, 2)
-    l1 = {}
-    for b, (kind, bid) in enumerate(jobs):
-        if kind == 1:
-            assert bid not in l1
-            l1[int(bid)] = b
-    assert sorted(l1) == list(range(2 * R))
-    seen = set()
-    for b, (kind, bid) in enumerate(jobs):
-        if kind != 2:
-            continue
-        assert bid not in seen
-        seen.add(int(bid))
-        r = int(bid) // 2 // P
-        for c in (0, 1):
-            p = l1[2 * r + c]
-            assert p < b and p % 8 == b % 8, f"layer-2 block {b} (row tile {r}) before its producer {p}"
-    assert sorted(seen) == list(range(2 * P * R))
-    assert set(jobs[:, 0].tolist()) <= {0, 1, 2}
-
-
-@pytest.mark.parametrize("P,lag", [(2, 10), (1, 10), (2, 1), (2, 3), (1, 4)])
-def test_persistent_layer_sequence(P, lag):
-    """The persistent one-grid kernel's per-XCD job sequence (chm_debug_layer_seq, the function the
-    kernel runs): every local row gets its 2 layer-1 tiles and its 2 P layer-2 tiles exactly once, column tile 0 of a row
-    (the job that claims a pool row) comes before its column tile 1, every layer-2 job of a row comes
-    after both of that row's layer-1 jobs (a layer-2 job's waits always point to jobs taken earlier),
-    and layer-2 rows never go back (the kernel's exit rule: once a layer-2 job's row is past the last
-    valid row, so is every later job's)."""
-    n = 6000
-    out = (ctypes.c_int64 * (3 * n))()
-    assert _lib.load().chm_debug_layer_seq(n, P, lag, out) == 0
-    jobs = [tuple(out[3 * k:3 * k + 3]) for k in range(n)]
-    seen = {}
-    for k, (kind, row, sub) in enumerate(jobs):
-        assert (kind, row, sub) not in seen
-        seen[(kind, row, sub)] = k
-        if kind == 1:
-            assert sub in (0, 1)
-            if sub == 1:
-                assert seen[(1, row, 0)] < k
-        else:
-            assert kind == 2 and 0 <= sub < 2 * P and row >= 0
-            assert seen[(1, row, 0)] < k and seen[(1, row, 1)] < k
-    rows2 = [row for kind, row, _ in jobs if kind == 2]
-    assert rows2 == sorted(rows2)
-    for r in range(max(rows2)):
-        assert all((2, r, s) in seen for s in range(2 * P)) and all((1, r, s) in seen for s in (0, 1))

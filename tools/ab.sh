@@ -1,7 +1,7 @@
 # Same-box A/B of launch options: bench.py under each environment setting in turn, R rounds alternating
 # (A B C A B C ...), so box drift hits every arm alike. Repo root, GPU box.
 #   bash tools/ab.sh <tag> <rounds> "<env A>" "<env B>" ... -- <bench args>
-# e.g. bash tools/ab.sh pool 2 "CHM_EDGE_POOL=15" "CHM_EDGE_POOL=0" -- --n-samples 64 --steps 20
+# e.g. bash tools/ab.sh lag 2 "CHM_EDGE_LAG=8" "CHM_EDGE_LAG=4" -- --n-samples 64 --steps 20
 # Prints one summary line per run (tools/bench_summary.py) and the per-arm median ms/step.
 TAG=$1; R=$2; shift 2
 ARMS=()
