@@ -16,10 +16,12 @@ from chemeleon_amd.symmetry import CRYSTAL_SYSTEMS, Symmetry, SymmetryReport, sy
 from chemeleon_amd.primitive import Primitive, PrimitiveReport, primitive_states  # noqa: F401
 from chemeleon_amd.match import Match, MatchReport, Reference, match_states  # noqa: F401
 from chemeleon_amd.match_group import MatchDedup, MatchGroupReport, match_group_states  # noqa: F401
+from chemeleon_amd.match_set import MatchSet, MatchSetReport, ReferenceSet, match_set_states  # noqa: F401
 
 __all__ = ["Chemeleon", "CSPNet", "DECODER_OUTPUTS", "Constraint", "Screen", "ScreenReport", "screen_states",
            "Dedup", "DedupReport", "Fingerprints", "dedup_states", "fingerprint_states", "group_fingerprints",
            "Cell", "CellReport", "cell_states", "reduce_states", "CRYSTAL_SYSTEMS", "Symmetry", "SymmetryReport",
            "symmetry_states", "Primitive", "PrimitiveReport", "primitive_states", "Match", "MatchReport", "Reference",
-           "match_states", "MatchDedup", "MatchGroupReport", "match_group_states"]
+           "match_states", "MatchDedup", "MatchGroupReport", "match_group_states", "MatchSet",
+           "MatchSetReport", "ReferenceSet", "match_set_states"]
 __version__ = "0.1.0"

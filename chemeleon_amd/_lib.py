@@ -246,6 +246,16 @@ SIGNATURES = {
                                     c_i64, c_void_p, c_i64, c_float, c_float, c_float, c_void_p, c_i64, c_void_p, c_i64,
                                     c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
                                     c_void_p]),
+    "chm_match_set_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_int32), c_int,
+                                     ctypes.POINTER(c_void_p)]),
+    "chm_match_set_destroy": (None, [c_void_p]),
+    "chm_match_set_num_pairs_max": (c_i64, [c_void_p]),
+    "chm_match_set_workspace_bytes": (ctypes.c_size_t, [c_void_p]),
+    "chm_match_set_run": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                  c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                  c_i64, c_float, c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
+                                  c_void_p, ctypes.c_size_t, c_void_p]),
     "chm_mt19937_uniform": (c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), c_i64, c_i64, c_i64, c_void_p]),
 }

@@ -739,3 +739,355 @@ extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_
   HIPCHK(hipGetLastError());
   return CHM_OK;
 }
+
+// ---- searching a reference set for each sample (chm_match_set_*): k_set_keys finds each sample's candidates in the
+// sorted set, k_set_offsets scans their counts, k_set_pairs runs match_block over the compact pair list on a grid
+// of fixed size and k_set_gather writes each sample's record against its winner
+namespace {
+
+constexpr unsigned long long kMixA = CHM_MATCH_SET_MIX_A, kMixB = CHM_MATCH_SET_MIX_B;
+
+__device__ inline unsigned long long mix_type(long long type) {
+  unsigned long long z = (unsigned long long)(unsigned)type + 1ull;  // (the low 32 bits, as match_block compares them)
+  z = (z ^ (z >> 30)) * kMixA;
+  z = (z ^ (z >> 27)) * kMixB;
+  return z ^ (z >> 31);
+}
+
+struct SetArgs {
+  int B;
+  const chm_cell_record* rec;           // [B] of the samples
+  const long long* types;               // [N]
+  const int* off;                       // [B + 1]
+  const unsigned char* exclude;         // NULL: none excluded
+  const int* size_first;                // [kMaxAtoms + 2]: the sorted positions of size n are [size_first[n], size_first[n + 1])
+  const unsigned long long* rkeys;      // [R] sorted within a size
+  const int* rindex;                    // [R] original index of sorted position
+  const int* rpos;                      // [R] sorted position of original index
+  unsigned long long* keys;             // [B]
+  unsigned long long* win;              // [B] (rms bits << 32) | original index of the best matched candidate
+  int* lo;                              // [B]
+  int* cnt;                             // [B]
+  int* n_matched;                       // [B]
+  int* first;                           // [B + 1]
+  const int4* pout;                     // [capacity]
+  int4* out;                            // [B] records of 48 bytes
+};
+
+// Block g = sample g: its key, its candidates [lo, lo + cnt) in the sorted set, and its winner word and match count
+// cleared in front of k_set_pairs (a kernel, not a memset node: the sequence is replayed from captured graphs).
+__global__ __launch_bounds__(kBlock) void k_set_keys(SetArgs p) {
+  __shared__ unsigned long long s_part[kBlock / 64];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = p.off[g], n = p.off[g + 1] - n0;  // (1 <= n <= kMaxAtoms: chm_match_set_create)
+  unsigned long long v = tid < n ? mix_type(p.types[(long)n0 + tid]) : 0ull;
+  // (wrapping integer adds in a fixed tree: lanes, then waves in index order)
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  if (lane == 0) s_part[wave] = v;
+  __syncthreads();
+  if (tid != 0) return;
+  unsigned long long key = s_part[0];
+  for (int w = 1; w < kBlock / 64; ++w) key += s_part[w];
+  int lo = 0, cnt = 0;
+  const bool out = (p.exclude && p.exclude[g]) || (p.rec[g].flags & kNoCell);
+  if (!out) {
+    const int a = p.size_first[n], b = p.size_first[n + 1];
+    int l = a, r = b;  // the first position in [a, b) whose key is >= key
+    while (l < r) {
+      const int m = l + (r - l) / 2;
+      if (p.rkeys[m] < key) l = m + 1; else r = m;
+    }
+    lo = l, r = b;     // the first position in [lo, b) whose key is > key
+    while (l < r) {
+      const int m = l + (r - l) / 2;
+      if (p.rkeys[m] <= key) l = m + 1; else r = m;
+    }
+    cnt = l - lo;
+  }
+  p.keys[g] = key;
+  p.lo[g] = lo;
+  p.cnt[g] = cnt;
+  p.win[g] = ~0ull;
+  p.n_matched[g] = 0;
+}
+
+// One block: first[B + 1] = the exclusive scan of cnt[B] (a chunked integer scan, as k_prim_offsets).
+__global__ __launch_bounds__(kBlock) void k_set_offsets(SetArgs p) {
+  __shared__ int s[kBlock];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    s_carry = 0;
+    p.first[0] = 0;
+  }
+  __syncthreads();
+  for (int base = 0; base < p.B; base += kBlock) {  // (B is the same in every thread: the barriers are uniform)
+    const int g = base + tid;
+    s[tid] = g < p.B ? p.cnt[g] : 0;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+      const int add = tid >= d ? s[tid - d] : 0;
+      __syncthreads();
+      s[tid] += add;
+      __syncthreads();
+    }
+    const int carry = s_carry;
+    if (g < p.B) p.first[g + 1] = carry + s[tid];
+    __syncthreads();
+    if (tid == kBlock - 1) s_carry = carry + s[tid];
+    __syncthreads();
+  }
+}
+
+struct SetPairArgs {
+  MatchArgs m;  // the reference side is the sorted set; ref_of, out and perm are unused
+  int B;
+  const int* first;          // [B + 1]; first[B] = P, the pairs of this run
+  const int* lo;             // [B]
+  const int* rindex;         // [R]
+  int4* pout;                // [capacity] {rms, max_dist, flags, matched}; [0, P) are written
+  int* n_matched;            // [B]
+  unsigned long long* win;   // [B]
+  unsigned* sink;            // one word that match_block or-s 0 into
+};
+
+// The blocks stride over the pairs b < P of this run: pair b is sample g = the last one with first[g] <= b against
+// the set's sorted position lo[g] + b - first[g]. The record at b depends on the two structures alone; a match adds
+// one to the sample's count and takes the integer minimum of (rms bits, original index) into its winner word.
+__global__ __launch_bounds__(kBlock) void k_set_pairs(SetPairArgs q) {
+  const int P = q.first[q.B];
+  for (int b = blockIdx.x; b < P; b += gridDim.x) {  // (b and everything derived from it are uniform over the block)
+    int g = 0, hi = q.B - 1;  // first[g] <= b < first[hi + 1]
+    while (g < hi) {
+      const int mid = g + (hi - g + 1) / 2;
+      if (q.first[mid] <= b) g = mid; else hi = mid - 1;
+    }
+    const int pos = q.lo[g] + (b - q.first[g]);
+    int4* oi = q.pout + b;
+    match_block<true>(q.m, g, pos, oi, q.sink, 0u);
+    if (threadIdx.x == 0) {
+      const int4 r = oi[0];
+      if (r.w) {
+        atomicAdd(q.n_matched + g, 1);
+        atomicMin(q.win + g, ((unsigned long long)(unsigned)r.x << 32) | (unsigned long long)(unsigned)q.rindex[pos]);
+      }
+    }
+    __syncthreads();  // (thread 0 has read the block's LDS before the next pair is staged)
+  }
+}
+
+// Thread g: the record of sample g against its winner.
+__global__ __launch_bounds__(kBlock) void k_set_gather(SetArgs p) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= p.B) return;
+  const unsigned long long w = p.win[g], key = p.keys[g];
+  const int first = p.first[g], lo = p.lo[g], cnt = p.cnt[g];
+  int4 a = make_int4(0, 0, 0, 0), b = make_int4(-1, -1, cnt, p.n_matched[g]);
+  a.z = ((p.exclude && p.exclude[g]) ? CHM_MATCH_EXCLUDED : 0) | ((p.rec[g].flags & kNoCell) ? CHM_MATCH_NO_LATTICE : 0);
+  if (w != ~0ull) {
+    const int ref = (int)(unsigned)(w & 0xffffffffull), pos = p.rpos[ref];
+    const int4 r = p.pout[first + (pos - lo)];
+    a = make_int4(r.x, r.y, r.z, 1);
+    b.x = ref, b.y = pos;
+  }
+  p.out[3 * (long)g] = a;
+  p.out[3 * (long)g + 1] = b;
+  p.out[3 * (long)g + 2] = make_int4((int)(unsigned)(key & 0xffffffffull), (int)(unsigned)(key >> 32), first, lo);
+}
+
+const chm::OffsetRule kSetLists{"match-set plan", kMaxAtoms, "the matcher"};
+const chm::Check set_check{"the match-set plan"};
+
+}  // namespace
+
+struct chm_match_set {
+  int B = 0, R = 0, grid = 0;
+  long N = 0, NR = 0, capacity = 0;
+  char* d_mem = nullptr;  // one allocation: rkeys [R] u64, then off [B + 1], roff [R + 1], rindex [R], rpos [R], size_first
+  const unsigned long long* d_rkeys = nullptr;
+  const int* d_off = nullptr;
+  const int* d_roff = nullptr;
+  const int* d_rindex = nullptr;
+  const int* d_rpos = nullptr;
+  const int* d_size_first = nullptr;
+};
+
+extern "C" int chm_match_set_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms,
+                                    const uint64_t* h_ref_keys, const int32_t* h_ref_index, int num_refs,
+                                    chm_match_set** out) {
+  static_assert(sizeof(chm_match_set_record) == 48, "the record is 48 bytes");
+  if (!out) return fail(CHM_E_ARG, "out is NULL");
+  *out = nullptr;
+  if (!h_natoms) return fail(CHM_E_ARG, "natoms is NULL");
+  if (!h_ref_natoms) return fail(CHM_E_ARG, "ref_natoms is NULL");
+  if (!h_ref_keys) return fail(CHM_E_ARG, "ref_keys is NULL");
+  if (!h_ref_index) return fail(CHM_E_ARG, "ref_index is NULL");
+  if (num_graphs <= 0) return fail(CHM_E_ARG, "num_graphs must be >= 1");
+  if (num_refs <= 0) return fail(CHM_E_ARG, "num_refs must be >= 1");
+  const int B = num_graphs, R = num_refs;
+  std::vector<int> offs, roffs;
+  long N = 0, NR = 0;
+  int rc;
+  if ((rc = chm::node_offsets(h_natoms, B, "natoms", kSetLists, offs, &N))) return rc;
+  if ((rc = chm::node_offsets(h_ref_natoms, R, "ref_natoms", kSetLists, roffs, &NR))) return rc;
+  std::vector<int> rpos((size_t)R, -1), size_first(kMaxAtoms + 2, 0);
+  for (int k = 0; k < R; ++k) {
+    const int at = h_ref_index[k];
+    if (at < 0 || at >= R || rpos[at] >= 0)
+      return fail(CHM_E_ARG, "ref_index[" + std::to_string(k) + "] = " + std::to_string(at) + ": not a permutation of [0, " +
+                                 std::to_string(R) + ")");
+    rpos[at] = k;
+    if (k) {
+      const bool ordered = h_ref_natoms[k - 1] != h_ref_natoms[k] ? h_ref_natoms[k - 1] < h_ref_natoms[k]
+                           : h_ref_keys[k - 1] != h_ref_keys[k]   ? h_ref_keys[k - 1] < h_ref_keys[k]
+                                                                  : h_ref_index[k - 1] < at;
+      if (!ordered)
+        return fail(CHM_E_ARG, "the reference set is not sorted by (atom count, key, index) at position " + std::to_string(k));
+    }
+    size_first[h_ref_natoms[k] + 1] += 1;
+  }
+  for (int n = 1; n <= kMaxAtoms + 1; ++n) size_first[n] += size_first[n - 1];  // (size_first[n] = references smaller than n)
+  long capacity = 0;
+  for (int g = 0; g < B; ++g) {
+    capacity += size_first[h_natoms[g] + 1] - size_first[h_natoms[g]];
+    if (capacity > INT32_MAX)
+      return fail(CHM_E_UNSUPPORTED, "more than 2^31 - 1 pairs of equal atom count: they do not fit the pair list");
+  }
+  int device = 0;
+  hipDeviceProp_t prop;
+  hipError_t e = hipGetDevice(&device);
+  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+  if (e != hipSuccess) return fail(CHM_E_HIP, std::string("chm_match_set_create: ") + hipGetErrorString(e));
+  const size_t keys_bytes = (size_t)R * sizeof(unsigned long long);
+  const size_t n_ints = (size_t)B + 1 + (size_t)R + 1 + 2 * (size_t)R + size_first.size();
+  std::vector<char> host(keys_bytes + n_ints * sizeof(int), 0);
+  memcpy(host.data(), h_ref_keys, keys_bytes);
+  int* hi = reinterpret_cast<int*>(host.data() + keys_bytes);
+  memcpy(hi, offs.data(), offs.size() * sizeof(int));
+  memcpy(hi + B + 1, roffs.data(), roffs.size() * sizeof(int));
+  memcpy(hi + B + 1 + R + 1, h_ref_index, (size_t)R * sizeof(int));
+  memcpy(hi + B + 1 + R + 1 + R, rpos.data(), (size_t)R * sizeof(int));
+  memcpy(hi + B + 1 + R + 1 + 2 * (size_t)R, size_first.data(), size_first.size() * sizeof(int));
+  void* d_mem = nullptr;
+  if ((rc = chm::upload(host.data(), host.size(), "chm_match_set_create", &d_mem))) return rc;
+  chm_match_set* p = new chm_match_set;
+  p->B = B, p->R = R, p->N = N, p->NR = NR, p->capacity = capacity;
+  const long full = (long)CHM_MATCH_SET_BLOCKS_PER_CU * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1);
+  p->grid = (int)(capacity < full ? capacity : full);
+  p->d_mem = static_cast<char*>(d_mem);
+  p->d_rkeys = reinterpret_cast<const unsigned long long*>(p->d_mem);
+  p->d_off = reinterpret_cast<const int*>(p->d_mem + keys_bytes);
+  p->d_roff = p->d_off + B + 1;
+  p->d_rindex = p->d_roff + R + 1;
+  p->d_rpos = p->d_rindex + R;
+  p->d_size_first = p->d_rpos + R;
+  *out = p;
+  return CHM_OK;
+}
+
+extern "C" void chm_match_set_destroy(chm_match_set* p) {
+  if (!p) return;
+  (void)hipFree(p->d_mem);
+  delete p;
+}
+
+extern "C" int64_t chm_match_set_num_pairs_max(const chm_match_set* p) { return p ? p->capacity : 0; }
+
+// keys [B] and winner words [B] (64 bits each), then lo [B], cnt [B], n_matched [B], first [B + 1] and the sink word
+extern "C" size_t chm_match_set_workspace_bytes(const chm_match_set* p) {
+  if (!p) return 0;
+  return align16(2 * (size_t)p->B * sizeof(unsigned long long) + (4 * (size_t)p->B + 2) * sizeof(int));
+}
+
+extern "C" int chm_match_set_run(const chm_match_set* p, const void* d_cell_records, size_t n_record_bytes,
+                                 const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                                 const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                                 size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                                 const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                                 int64_t n_ref_lattices, const uint8_t* d_exclude, int64_t n_exclude, float ltol,
+                                 float stol, float angle_tol, void* d_out, size_t n_out_bytes, void* d_pair_records,
+                                 size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!p) return fail(CHM_E_ARG, "match-set plan is NULL");
+  const chm::Check& check = set_check;
+  int rc;
+  if ((rc = check.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_cell_records, "cell records"))) return rc;
+  if ((rc = check.count(d_atom_types, n_atom_types, p->N, "atom_types [N]"))) return rc;
+  if ((rc = check.count(d_frac, n_frac, 3 * p->N, "frac [N,3]"))) return rc;
+  if ((rc = check.count(d_lattices, n_lattices, 9L * p->B, "lattices [B,3,3]"))) return rc;
+  if ((rc = check.count(d_ref_cell_records, (long)n_ref_record_bytes, 128L * p->R, "ref cell records", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_ref_cell_records, "ref cell records"))) return rc;
+  if ((rc = check.count(d_ref_atom_types, n_ref_atom_types, p->NR, "ref_atom_types [NR]"))) return rc;
+  if ((rc = check.count(d_ref_frac, n_ref_frac, 3 * p->NR, "ref_frac [NR,3]"))) return rc;
+  if ((rc = check.count(d_ref_lattices, n_ref_lattices, 9L * p->R, "ref_lattices [R,3,3]"))) return rc;
+  if ((rc = check.optional(d_exclude, n_exclude, p->B, "exclude [B]"))) return rc;
+  if ((rc = check.range(ltol, CHM_MATCH_MAX_LTOL, "ltol", ""))) return rc;
+  if ((rc = check.range(stol, CHM_MATCH_MAX_STOL, "stol", ""))) return rc;
+  if ((rc = check.range(angle_tol, CHM_MATCH_MAX_ANGLE_TOL, "angle_tol", " degrees"))) return rc;
+  if ((rc = check.count(d_out, (long)n_out_bytes, 48L * p->B, "out", "bytes"))) return rc;
+  if ((rc = check.aligned16(d_out, "out"))) return rc;
+  if (p->capacity == 0) {
+    if (n_pair_bytes != 0) return fail(CHM_E_ARG, "pair records: " + std::to_string(n_pair_bytes) + " bytes, the plan has no pair");
+  } else if ((rc = check.count(d_pair_records, (long)n_pair_bytes, 16L * p->capacity, "pair records", "bytes"))) {
+    return rc;
+  }
+  if ((rc = check.aligned16(d_pair_records, "pair records"))) return rc;
+  if ((rc = check.workspace(d_workspace, workspace_bytes, chm_match_set_workspace_bytes(p)))) return rc;
+  if ((rc = check.aligned16(d_workspace, "workspace"))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int B = p->B;
+  SetArgs a;
+  a.B = B;
+  a.rec = static_cast<const chm_cell_record*>(d_cell_records);
+  a.types = reinterpret_cast<const long long*>(d_atom_types);
+  a.off = p->d_off;
+  a.exclude = d_exclude;
+  a.size_first = p->d_size_first;
+  a.rkeys = p->d_rkeys;
+  a.rindex = p->d_rindex;
+  a.rpos = p->d_rpos;
+  a.keys = static_cast<unsigned long long*>(d_workspace);
+  a.win = a.keys + B;
+  a.lo = reinterpret_cast<int*>(a.win + B);
+  a.cnt = a.lo + B;
+  a.n_matched = a.cnt + B;
+  a.first = a.n_matched + B;
+  a.pout = static_cast<const int4*>(d_pair_records);
+  a.out = static_cast<int4*>(d_out);
+  hipLaunchKernelGGL(k_set_keys, dim3((unsigned)B), dim3(kBlock), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_set_offsets, dim3(1), dim3(kBlock), 0, s, a);
+  HIPCHK(hipGetLastError());
+  if (p->capacity) {
+    SetPairArgs q;
+    q.m.rec = a.rec;
+    q.m.types = a.types;
+    q.m.x = d_frac;
+    q.m.lat = d_lattices;
+    q.m.off = p->d_off;
+    q.m.rrec = static_cast<const chm_cell_record*>(d_ref_cell_records);
+    q.m.rtypes = reinterpret_cast<const long long*>(d_ref_atom_types);
+    q.m.rx = d_ref_frac;
+    q.m.rlat = d_ref_lattices;
+    q.m.roff = p->d_roff;
+    q.m.ref_of = nullptr;
+    q.m.ltol = ltol;
+    q.m.stol = stol;
+    q.m.angle_tol = angle_tol;
+    q.m.out = nullptr;
+    q.m.perm = nullptr;
+    q.B = B;
+    q.first = a.first;
+    q.lo = a.lo;
+    q.rindex = p->d_rindex;
+    q.pout = static_cast<int4*>(d_pair_records);
+    q.n_matched = a.n_matched;
+    q.win = a.win;
+    q.sink = reinterpret_cast<unsigned*>(a.first + B + 1);
+    hipLaunchKernelGGL(k_set_pairs, dim3((unsigned)p->grid), dim3(kBlock), 0, s, q);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_set_gather, dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return CHM_OK;
+}

@@ -330,7 +330,7 @@ at::Tensor d3pm_sample(const at::Tensor& logits, const at::Tensor& xt, const at:
 }
 
 // ---------------------------------------------------------------- finishing legs
-// screen, dedup, cell, symmetry, primitive, match and match_group share what stands between here and the first of them:
+// screen, dedup, cell, symmetry, primitive, match, match_group and match_set share what stands between here and the first of them:
 // the checks of a state against its crystal list, the optional exclude / require tensors, and one plan cache.
 // A cache keeps the plans of the last 8 (crystal lists, device) keys, evicts the oldest first and lives as long
 // as the process (nothing is freed during static destruction, when the HIP runtime may be gone). It hands out
@@ -722,6 +722,68 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> match_group(const at:
   return {group, count, rec, pairs};
 }
 
+// Searching a reference set (chm_cell_run on both lists + chm_match_set_run on one stream): (records uint8 [B,48] =
+// the chm_match_set_record of every crystal, pair records uint8 [num_pairs_max,16]: the first sum(n_candidates) are
+// this run's, the rest is 0). The references come sorted by (atom count, key, index) with their keys (int64 holding
+// the 64 bits) and original indices; the plan's key is (natoms, ref_natoms, ref_keys, ref_index).
+struct MatchSetPlan {
+  CellHandle cells, ref_cells;
+  Handle<chm_match_set, chm_match_set_destroy> set;
+  void create(const Lists& key) {
+    const auto nat = to_int32(key[0], "match_set", "crystal"), rnat = to_int32(key[1], "match_set", "reference");
+    std::vector<uint64_t> keys(key[2].begin(), key[2].end());
+    std::vector<int32_t> index(key[3].begin(), key[3].end());
+    int rc = chm_match_set_create(nat.data(), (int)nat.size(), rnat.data(), keys.data(), index.data(), (int)rnat.size(),
+                                  &set.p);
+    if (rc == CHM_OK) rc = chm_cell_create(nat.data(), (int)nat.size(), &cells.p);
+    if (rc == CHM_OK) rc = chm_cell_create(rnat.data(), (int)rnat.size(), &ref_cells.p);
+    check(rc, "chm_match_set_create");
+  }
+};
+
+std::tuple<at::Tensor, at::Tensor> match_set(const at::Tensor& atom_types, const at::Tensor& frac,
+                                             const at::Tensor& lattices, std::vector<int64_t> natoms,
+                                             const at::Tensor& ref_atom_types, const at::Tensor& ref_frac,
+                                             const at::Tensor& ref_lattices, std::vector<int64_t> ref_natoms,
+                                             std::vector<int64_t> ref_keys, std::vector<int64_t> ref_index,
+                                             const c10::optional<at::Tensor>& exclude, double ltol, double stol,
+                                             double angle_tol) {
+  TORCH_CHECK(!natoms.empty(), "match_set: natoms is empty");
+  TORCH_CHECK(!ref_natoms.empty(), "match_set: ref_natoms is empty");
+  TORCH_CHECK(ref_keys.size() == ref_natoms.size(), "ref_keys: expected ", ref_natoms.size(), " entries, got ", ref_keys.size());
+  TORCH_CHECK(ref_index.size() == ref_natoms.size(), "ref_index: expected ", ref_natoms.size(), " entries, got ",
+              ref_index.size());
+  const c10::Device dev = frac.device();
+  need_crystals_on(dev, &atom_types, frac, lattices);
+  need_crystals_on(dev, &ref_atom_types, ref_frac, ref_lattices, "ref_");
+  const Crystals c = need_crystals_shape(natoms, &atom_types, frac, lattices);
+  const int64_t R = need_crystals_shape(ref_natoms, &ref_atom_types, ref_frac, ref_lattices, "ref_").B;
+  const uint8_t* ex = optional_exclude(exclude, dev, c.B);
+  HIPGuardMasqueradingAsCUDA guard(dev);
+  const auto plan = cached_plan<MatchSetPlan>({natoms, ref_natoms, ref_keys, ref_index}, dev.index());
+  const int64_t P = chm_match_set_num_pairs_max(plan->set.p);
+  const size_t ws_bytes = chm_match_set_workspace_bytes(plan->set.p);
+  const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+  at::Tensor cells = at::empty({c.B, 128}, bytes), ref_cells = at::empty({R, 128}, bytes), rec = at::empty({c.B, 48}, bytes),
+             pairs = at::zeros({P, 16}, bytes), ws = at::empty({(int64_t)ws_bytes}, bytes);
+  check(chm_cell_run(plan->cells.p, lattices.data_ptr<float>(), lattices.numel(), nullptr, 0, kMatchCellSymprec,
+                     kMatchCellAngleTolerance, cells.data_ptr(), (size_t)cells.numel(), stream()),
+        "chm_cell_run");
+  check(chm_cell_run(plan->ref_cells.p, ref_lattices.data_ptr<float>(), ref_lattices.numel(), nullptr, 0,
+                     kMatchCellSymprec, kMatchCellAngleTolerance, ref_cells.data_ptr(), (size_t)ref_cells.numel(),
+                     stream()),
+        "chm_cell_run");
+  check(chm_match_set_run(plan->set.p, cells.data_ptr(), (size_t)cells.numel(), atom_types.data_ptr<int64_t>(),
+                          atom_types.numel(), frac.data_ptr<float>(), frac.numel(), lattices.data_ptr<float>(),
+                          lattices.numel(), ref_cells.data_ptr(), (size_t)ref_cells.numel(),
+                          ref_atom_types.data_ptr<int64_t>(), ref_atom_types.numel(), ref_frac.data_ptr<float>(),
+                          ref_frac.numel(), ref_lattices.data_ptr<float>(), ref_lattices.numel(), ex, ex ? c.B : 0,
+                          (float)ltol, (float)stol, (float)angle_tol, rec.data_ptr(), (size_t)rec.numel(),
+                          P ? pairs.data_ptr() : nullptr, (size_t)pairs.numel(), ws.data_ptr(), ws_bytes, stream()),
+        "chm_match_set_run");
+  return {rec, pairs};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(chemeleon, m) {
@@ -761,6 +823,9 @@ TORCH_LIBRARY(chemeleon, m) {
         "(Tensor, Tensor)");
   m.def("match_group(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor? exclude, float ltol, "
         "float stol, float angle_tol) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("match_set(Tensor atom_types, Tensor frac, Tensor lattices, int[] natoms, Tensor ref_atom_types, Tensor ref_frac, "
+        "Tensor ref_lattices, int[] ref_natoms, int[] ref_keys, int[] ref_index, Tensor? exclude, float ltol, float stol, "
+        "float angle_tol) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
@@ -775,4 +840,5 @@ TORCH_LIBRARY_IMPL(chemeleon, CUDA, m) {
   m.impl("primitive", primitive);
   m.impl("match", match);
   m.impl("match_group", match_group);
+  m.impl("match_set", match_set);
 }

@@ -1,6 +1,6 @@
 """The tail of Chemeleon.sample(): the optional legs that run on the finished state on the device (the screen,
 chemeleon_amd.screening; the primitive cell, chemeleon_amd.primitive; the cell, chemeleon_amd.cell; the symmetry, chemeleon_amd.symmetry; the matching,
-chemeleon_amd.match; the grouping, chemeleon_amd.dedup or, with a MatchDedup, chemeleon_amd.match_group), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
+chemeleon_amd.match; the search of a reference set, chemeleon_amd.match_set; the grouping, chemeleon_amd.dedup or, with a MatchDedup, chemeleon_amd.match_group), in one function. screened_atoms, deduped_atoms and finished_atoms of those modules call it."""
 
 from typing import Sequence
 
@@ -8,13 +8,14 @@ import numpy as np
 
 
 def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, screen=None, cell=None, symmetry=None,
-                 dedup=None, match=None, primitive=None):
+                 dedup=None, match=None, primitive=None, search=None):
     """(structures, reports): the tail of sample() with any of its optional legs, in this order: the screen,
     the primitive cell (which replaces the state for every leg after it and for the structures returned),
-    the cell, the symmetry, the matching, then the grouping, from which the failures of the first four (a screen
-    flag; a required lattice system or crystal system not met; with match.require, no match) are excluded. Only the structures that pass (with dedup:
+    the cell, the symmetry, the matching, the search of a reference set, then the grouping, from which the failures of
+    the legs before it (a screen flag; a required lattice system or crystal system not met; with match.require, no
+    match; with search.require, a sample that is not "known" / not "novel") are excluded. Only the structures that pass (with dedup:
     one representative per group) are copied and converted (in their reduced cells with cell.reduce), each with
-    atoms.info["screen"] / ["primitive"] / ["cell"] / ["symmetry"] / ["match"] / ["dedup"] for the legs that ran.
+    atoms.info["screen"] / ["primitive"] / ["cell"] / ["symmetry"] / ["match"] / ["search"] / ["dedup"] for the legs that ran.
     `reports` is a dict with the report of each leg that ran under the same names."""
     from chemeleon_amd.screening import screen_states, selected_atoms
     nat = [int(n) for n in natoms]
@@ -43,6 +44,11 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
         reports["match"] = match_states(nat, atom_types, frac_coords, lattices, match)
         if match.require:
             failed = reports["match"].mismatch.copy() if failed is None else failed | reports["match"].mismatch
+    if search is not None:
+        from chemeleon_amd.match_set import match_set_states
+        reports["search"] = match_set_states(nat, atom_types, frac_coords, lattices, search)
+        if search.require is not None:
+            failed = reports["search"].mismatch.copy() if failed is None else failed | reports["search"].mismatch
     if dedup is not None:
         from chemeleon_amd.match_group import MatchDedup, match_group_states
         if isinstance(dedup, MatchDedup):  # (grouping by matching instead of by fingerprints)
@@ -69,6 +75,8 @@ def finish_atoms(natoms: Sequence[int], atom_types, frac_coords, lattices, scree
             at.info["symmetry"] = dict(reports["symmetry"].record(g), index=g)
         if "match" in reports:
             at.info["match"] = dict(reports["match"].record(g), index=g)
+        if "search" in reports:
+            at.info["search"] = dict(reports["search"].record(g), index=g)
         if "dedup" in reports:
             at.info["dedup"] = reports["dedup"].record(g)
     return atoms, reports

@@ -62,6 +62,7 @@ class Chemeleon(nn.Module):
     last_symmetry = None  # the SymmetryReport of the last sample(..., symmetry=...) call
     last_primitive = None  # the PrimitiveReport of the last sample(..., primitive=...) call
     last_match = None  # the MatchReport of the last sample(..., match=...) call
+    last_search = None  # the MatchSetReport of the last sample(..., search=...) call
 
     def __init__(self, _config: Dict[str, Any], text_encoder=None, **kwargs):
         super().__init__()
@@ -653,7 +654,7 @@ class Chemeleon(nn.Module):
     def sample(self, text_input: str, n_atoms: int, n_samples: int, cond_scale: float = 2.0, step_lr: float = 1e-5,
                return_trajectory: bool = False, stream: bool = False, *, distributed: Optional[bool] = None,
                group=None, overlap: bool = True, screen=None, dedup=None, cell=None, symmetry=None,
-               match=None, primitive=None, **kw):
+               match=None, primitive=None, search=None, **kw):
         """chemeleon.py:469-490. Without return_trajectory / stream, only the
         final state is copied to the host (the reference converts every step).
         Keyword arguments go to sample_states: noise="philox" (device noise)
@@ -721,8 +722,28 @@ class Chemeleon(nn.Module):
         atoms.info["primitive"]; the whole report is kept as self.last_primitive. A structure without
         translations comes back as it is, in its Niggli-reduced basis. Like the screen it is for finished
         structures (ValueError with stream / return_trajectory) and runs on the gathered final state on every
-        rank. Without the keyword nothing of it runs."""
+        rank. Without the keyword nothing of it runs.
+
+        search=MatchSet(...) (chemeleon_amd.match_set): a whole set of reference structures is searched for every
+        finished structure on the device (the references of its atom count and composition, each one match in the
+        definition of match=), after the matching and before the grouping; each returned structure gets
+        atoms.info["search"] ("known", "novel", "ref", "rms", ...) and the whole report is kept as
+        self.last_search (novelty_rate). With require="novel" only the structures found nowhere in the set are
+        returned, with require="known" only the ones found, and the others take no part in the grouping: screen=,
+        search=MatchSet(known, require="novel") and dedup=MatchDedup() together return the valid, novel, unique
+        structures. Like the screen it is for finished structures (ValueError with stream / return_trajectory)
+        and runs on the gathered final state on every rank, with no collective of its own. Without the keyword
+        nothing of it runs."""
         natoms = [n_atoms] * n_samples
+        if search is not None:
+            from chemeleon_amd.match import MAX_ATOMS as MATCH_MAX_ATOMS
+            from chemeleon_amd.match_set import MatchSet
+            if not isinstance(search, MatchSet):
+                raise ValueError("search must be a chemeleon_amd.MatchSet")
+            if stream or return_trajectory:
+                raise ValueError("search= applies to finished structures: not with stream / return_trajectory")
+            if n_atoms > MATCH_MAX_ATOMS:
+                raise ValueError(f"search= holds at most {MATCH_MAX_ATOMS} atoms per crystal, got n_atoms={n_atoms}")
         if primitive is not None:
             from chemeleon_amd.primitive import MAX_ATOMS as PRIMITIVE_MAX_ATOMS
             from chemeleon_amd.primitive import Primitive
@@ -795,10 +816,10 @@ class Chemeleon(nn.Module):
             pass
         _, a, x, lat = last
         if screen is not None or cell is not None or symmetry is not None or dedup is not None or match is not None \
-                or primitive is not None:
+                or primitive is not None or search is not None:
             from chemeleon_amd.finish import finish_atoms
             atoms, reports = finish_atoms(natoms, a, x, lat, screen=screen, cell=cell, symmetry=symmetry, dedup=dedup,
-                                          match=match, primitive=primitive)
+                                          match=match, primitive=primitive, search=search)
             for leg, report in reports.items():  # (only the legs that were asked for: the others keep their last)
                 setattr(self, "last_" + leg, report)
             return atoms

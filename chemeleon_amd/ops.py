@@ -9,6 +9,8 @@
     torch.ops.chemeleon.sample_step(batch, sched, t, 2.0, a, x, lat, cond, null, None, None, None, None, 0, 0, 0)
 
     group, count, records, pairs = torch.ops.chemeleon.match_group(a, x, lat, natoms, None, 0.2, 0.3, 5.0)
+    records, pairs = torch.ops.chemeleon.match_set(a, x, lat, natoms, ref_a, ref_x, ref_lat, ref_natoms, ref_keys,
+                                                   ref_index, None, 0.2, 0.3, 5.0)   # a sorted ReferenceSet's lists
 
 The classes own the library's objects (reference-counted: a Batch holds its Model, a Schedule its
 tables), so TorchScript and C++ callers build and drive the sampler with no ctypes object in sight.

@@ -1225,6 +1225,91 @@ int chm_match_group_run(const chm_match_group* plan, const void* d_cell_records,
                         int64_t n_count, void* d_out, size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes,
                         void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Searching a set of reference structures for each finished structure on the device: is this sample any structure
+ * of the set (known) or none of them (novel)? It is what the users of the reference's
+ * scripts/navigate_chemical_system.py do with its output (strike out the training set, or merge a run into the
+ * representatives kept so far) with the match criterion above. This is NOT a port of pymatgen, and how far known /
+ * novel agree with StructureMatcher().fit against every structure of the set has not been measured. It inherits
+ * every caveat of chm_match_*: atom counts must be equal (no reduction to a primitive cell: chm_prim_* first is the
+ * way round it), and the pairing is the nearest-partner rule, not an optimal assignment.
+ *
+ * Composition key. key = sum_i mix(t_i) over the atoms of a structure, as wrapping 64-bit unsigned addition, where
+ * t_i is the atom type's low 32 bits as an unsigned number (what the matcher compares) and mix is the splitmix64
+ * finaliser of t + 1: z = t + 1; z = (z ^ (z >> 30)) * CHM_MATCH_SET_MIX_A; z = (z ^ (z >> 27)) *
+ * CHM_MATCH_SET_MIX_B; mix = z ^ (z >> 31). The key is exact and does not depend on the order of the atoms; equal
+ * compositions have equal keys. Two different compositions of one atom count with equal keys cost one launched
+ * pair that ends with CHM_MATCH_COMPOSITION: a collision can never hide a match.
+ *
+ * Reference set. R structures of at most 256 atoms each, packed like a state and held sorted ascending by (atom
+ * count, key, original index); ref_index[k] is the original index of sorted position k. The caller sorts and
+ * computes the keys of the references on the host, once; the keys of the samples are computed on the device in
+ * every run, from the state's atom types as they are then.
+ *
+ * Candidates of sample g: the references with its atom count and its key, one contiguous range [lo_g, lo_g + c_g)
+ * of sorted positions. An excluded sample (d_exclude[g] != 0; NULL with n_exclude = 0: none) and a sample whose
+ * cell record has CHM_CELL_NOT_REDUCED, DEGENERATE or NONFINITE have no candidates (c_g = 0) and the flags
+ * CHM_MATCH_EXCLUDED / CHM_MATCH_NO_LATTICE. The pairs of a run are the candidates of sample 0, then of sample 1,
+ * ..., each in sorted order: P = sum_g c_g of them, first_g = sum_{h < g} c_h. P is known on the device only; it is
+ * at most chm_match_set_num_pairs_max = the sum over the samples of the number of references of that atom count,
+ * which the host knows at create and which the pair list can never overflow.
+ *
+ * Pair match. Each pair is one match in chm_match_*'s definition, word for word (the same device code), the
+ * reference being the reference side: l and CHM_MATCH_THIN come from it. Its record is a chm_match_pair_record
+ * {rms, max_dist, flags, matched} at its position in the pair list and depends on the two structures and the
+ * tolerances alone. A reference without a reduced cell matches nothing (CHM_MATCH_NO_LATTICE on its pairs).
+ *
+ * Record per sample (48 bytes): n_candidates = c_g; n_matched = how many of them matched; known = n_matched > 0;
+ * the winner = the matched candidate with the smallest rms, ties to the smallest original index (an integer
+ * minimum over (rms bits, original index), so the answer does not depend on how the set was ordered): ref = its
+ * original index, position = its sorted position (both -1 when novel), rms, max_dist and flags of its pair record
+ * (rms = max_dist = 0 when novel; flags then hold only CHM_MATCH_EXCLUDED / NO_LATTICE of the sample); key; first
+ * = first_g and lo = lo_g, so that the sample's pair records are [first, first + n_candidates) for the sorted
+ * positions lo, lo + 1, ...
+ *
+ * The run enqueues four kernels: the keys (one block per sample: a wave reduction and LDS, integer adds in a fixed
+ * order, two binary searches, and the sample's winner word and count cleared), the offsets (one block, an integer
+ * scan), the pairs (a grid of fixed size chosen at create, min(num_pairs_max, CHM_MATCH_SET_BLOCKS_PER_CU x the
+ * device's compute units) blocks that stride over b < P; one integer atomicAdd and one 64-bit atomicMin per match,
+ * no float atomics) and the gather (one thread per sample, blocks of 256). It takes every buffer with its count
+ * (cell records 128 bytes per structure, out 48 bytes per sample, pair records 16 bytes x num_pairs_max, NULL with
+ * 0 bytes when that is 0; all 16-byte aligned; the workspace at least chm_match_set_workspace_bytes); a NULL
+ * pointer, a mismatched count or a tolerance outside chm_match_run's ranges return CHM_E_ARG naming the argument
+ * before the first HIP call and nothing is enqueued. Pair records at and after P are left as they were. It
+ * allocates nothing and does not synchronise: legal under stream capture, and a replay follows the atom types,
+ * coordinates and cell records that the buffers hold then. Create refuses a structure of more than 256 atoms and
+ * more than 2^31 - 1 pairs with CHM_E_UNSUPPORTED, a set that is not sorted or a ref_index that is no permutation
+ * with CHM_E_ARG. */
+#define CHM_MATCH_SET_MIX_A 0xbf58476d1ce4e5b9ull
+#define CHM_MATCH_SET_MIX_B 0x94d049bb133111ebull
+#define CHM_MATCH_SET_BLOCKS_PER_CU 3 /* what the pair kernel's 144 VGPRs let a CU hold: three blocks of four waves */
+typedef struct {
+  float rms;            /* of the winner, in units of l of that reference; 0 when novel */
+  float max_dist;       /* of the winner (A) */
+  int32_t flags;        /* CHM_MATCH_* bits of the winner's pair, or EXCLUDED / NO_LATTICE of the sample */
+  int32_t known;        /* 1 or 0 */
+  int32_t ref;          /* the winner's original index, or -1 */
+  int32_t position;     /* the winner's sorted position, or -1 */
+  int32_t n_candidates; /* c_g */
+  int32_t n_matched;
+  uint64_t key;         /* the sample's composition key */
+  int32_t first;        /* the sample's first pair record */
+  int32_t lo;           /* the sorted position of its first candidate (where its key would stand if it has none) */
+} chm_match_set_record; /* 48 bytes */
+typedef struct chm_match_set chm_match_set;
+int chm_match_set_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms,
+                         const uint64_t* h_ref_keys, const int32_t* h_ref_index, int num_refs, chm_match_set** out);
+void chm_match_set_destroy(chm_match_set* plan);
+int64_t chm_match_set_num_pairs_max(const chm_match_set* plan);
+size_t chm_match_set_workspace_bytes(const chm_match_set* plan);
+int chm_match_set_run(const chm_match_set* plan, const void* d_cell_records, size_t n_record_bytes,
+                      const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                      const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                      size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                      const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices, int64_t n_ref_lattices,
+                      const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol, float angle_tol, void* d_out,
+                      size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
 int64_t chm_batch_num_edges(const chm_batch* b);
