@@ -238,6 +238,10 @@ SIGNATURES = {
     "chm_match_run": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                               c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_float,
                               c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p]),
+    "chm_match_run_pairing": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                      c_i64, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                      c_float, c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p,
+                                      c_int]),
     "chm_match_group_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(c_void_p)]),
     "chm_match_group_destroy": (None, [c_void_p]),
     "chm_match_group_num_pairs": (c_i64, [c_void_p]),
@@ -246,6 +250,10 @@ SIGNATURES = {
                                     c_i64, c_void_p, c_i64, c_float, c_float, c_float, c_void_p, c_i64, c_void_p, c_i64,
                                     c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
                                     c_void_p]),
+    "chm_match_group_run_pairing": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64,
+                                            c_void_p, c_i64, c_void_p, c_i64, c_float, c_float, c_float, c_void_p, c_i64,
+                                            c_void_p, c_i64, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
+                                            c_void_p, ctypes.c_size_t, c_void_p, c_int]),
     "chm_match_set_create": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int, ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_int32), c_int,
                                      ctypes.POINTER(c_void_p)]),
@@ -256,6 +264,10 @@ SIGNATURES = {
                                   c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
                                   c_i64, c_float, c_float, c_float, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
                                   c_void_p, ctypes.c_size_t, c_void_p]),
+    "chm_match_set_run_pairing": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                          c_i64, c_void_p, ctypes.c_size_t, c_void_p, c_i64, c_void_p, c_i64, c_void_p,
+                                          c_i64, c_void_p, c_i64, c_float, c_float, c_float, c_void_p, ctypes.c_size_t,
+                                          c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, c_int]),
     "chm_mt19937_uniform": (c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), c_i64, c_i64, c_i64, c_void_p]),
 }

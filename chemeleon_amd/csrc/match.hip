@@ -166,6 +166,171 @@ __device__ inline double det3(const float* L) {
   return (l[0] * (l[4] * l[8] - l[5] * l[7]) - l[1] * (l[3] * l[8] - l[5] * l[6])) + l[2] * (l[3] * l[7] - l[4] * l[6]);
 }
 
+// ---- optimal assignment of a collided candidate (pairing = CHM_MATCH_PAIRING_ASSIGNMENT), one wave per candidate
+constexpr int kMaxAssign = CHM_MATCH_MAX_ASSIGN;
+constexpr int kBitWords = kMaxMaps * kMaxAtoms / 32;  // one bit per candidate (M, t_j)
+
+// LDS of one wave: y (the mapped, shifted sample coordinates), the duals u (rows) and v (columns), minv, way and
+// row_of_col of the shortest-augmenting-path search, and col (row -> column, in the block's freed "taken" words)
+struct AssignLds {
+  float* y;  // [3 * kMaxAtoms]
+  float* u;
+  float* v;
+  float* minv;
+  int* way;
+  int* row_of_col;
+  int* col;
+};
+
+// The lanes of one wave see each other's LDS writes behind this (LDS operations of a wave complete in order).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// D = (y_i - xr_k) - rintf(y_i - xr_k) and |D|^2, the arithmetic of nearest()
+__device__ __forceinline__ float pair_cost(const float* y, int i, const Atom& b, const float* g, float* D) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    D[k] = y[3 * i + k] - b.x[k];
+    D[k] -= rintf(D[k]);
+  }
+  return norm2(g, D);
+}
+
+// The type-preserving bijection of minimal sum |D|^2 under (Minv, t, g) by shortest augmenting paths, and its score.
+// Every lane of the wave calls it with the same arguments. Every loop is bounded by n: a row whose search finds no
+// column (NaN or Inf costs) ends the solve with false. On true L.col[k] is reference atom k's sample atom and
+// (*rms, *maxq) the score, the same in every lane.
+__device__ bool assign_solve(const Atom* s_s, const Atom* s_r, const int n, const float* Minv, const float* t, const float* g,
+                             const AssignLds& L, const int lane, const float ell, float* rms, float* maxq) {
+  for (int i = lane; i < n; i += 64) {
+    float xm[3];
+    mapped(Minv, s_s[i].x, xm);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) L.y[3 * i + k] = xm[k] - t[k];
+    L.v[i] = 0.f;
+    L.row_of_col[i] = -1;
+  }
+  wave_sync();
+  // the dual start: u_k = the row minimum (ties: the smallest column), v = 0
+  for (int k = lane; k < n; k += 64) {
+    const Atom b = s_r[k];
+    float best = INFINITY;
+    int bi = -1;
+    for (int i = 0; i < n; ++i) {
+      if (s_s[i].type != b.type) continue;
+      float D[3];
+      const float q = pair_cost(L.y, i, b, g, D);
+      if (q < best) best = q, bi = i;
+    }
+    L.u[k] = best;
+    L.col[k] = bi;
+    if (bi >= 0) atomicMin(reinterpret_cast<unsigned*>(L.row_of_col) + bi, (unsigned)k);  // (-1 is the largest unsigned)
+  }
+  wave_sync();
+  // a column keeps the smallest row that wants it: the non-colliding row minima are placed
+  bool whole = true;
+  for (int k = lane; k < n; k += 64) {
+    const int bi = L.col[k];
+    if (bi < 0) whole = false;
+    else if (L.row_of_col[bi] != k) L.col[k] = -1;
+  }
+  if (__ballot(!whole)) return false;  // (a row without a finite cost: the prefilter lets none through)
+  wave_sync();
+  for (int i = 0; i < n; ++i) {
+    if (L.col[i] >= 0) continue;  // (uniform: from LDS behind wave_sync)
+    const int ty = s_r[i].type;
+    unsigned used = 0u;  // bit q: column lane + 64 q is in the tree
+#pragma unroll
+    for (int q = 0; q < kMaxAtoms / 64; ++q)
+      if (lane + 64 * q < n) L.minv[lane + 64 * q] = INFINITY;
+    int i0 = i, j0 = -1;
+    bool reached = false;
+    for (int step = 0; step < n; ++step) {  // (every step puts one more column into the tree)
+      const Atom b = s_r[i0];
+      const float ui0 = L.u[i0];
+      float ld = INFINITY;
+      int lj = INT_MAX;
+#pragma unroll
+      for (int q = 0; q < kMaxAtoms / 64; ++q) {
+        const int j = lane + 64 * q;
+        if (j >= n || ((used >> q) & 1u) || s_s[j].type != ty) continue;
+        float D[3];
+        const float cur = (pair_cost(L.y, j, b, g, D) - ui0) - L.v[j];
+        float mv = L.minv[j];
+        if (cur < mv) {
+          mv = cur;
+          L.minv[j] = cur;
+          L.way[j] = j0;
+        }
+        if (mv < ld) ld = mv, lj = j;
+      }
+      for (int d = 32; d >= 1; d >>= 1) {  // the minimum over the wave, ties to the smallest column
+        const float od = __shfl_xor(ld, d, 64);
+        const int oj = __shfl_xor(lj, d, 64);
+        if (od < ld || (od == ld && oj < lj)) ld = od, lj = oj;
+      }
+      if (lj == INT_MAX) break;  // no column left with a finite reduced cost
+      if (lane == 0) L.u[i] += ld;
+#pragma unroll
+      for (int q = 0; q < kMaxAtoms / 64; ++q) {
+        const int j = lane + 64 * q;
+        if (j >= n || s_s[j].type != ty) continue;
+        if ((used >> q) & 1u) {
+          L.u[L.row_of_col[j]] += ld;  // (the rows of the tree's columns are all different)
+          L.v[j] -= ld;
+        } else {
+          L.minv[j] -= ld;
+        }
+      }
+      if ((lj & 63) == lane) used |= 1u << (lj >> 6);
+      wave_sync();
+      j0 = lj;
+      const int r = L.row_of_col[lj];
+      if (r < 0) {
+        reached = true;
+        break;
+      }
+      i0 = r;
+    }
+    if (!reached) return false;  // (uniform: lj and r are the same in every lane)
+    if (lane == 0) {
+      int j = j0;
+      for (int s = 0; s < n && j >= 0; ++s) {  // back along the path: every column takes the row of the one before
+        const int jp = L.way[j];
+        const int row = jp < 0 ? i : L.row_of_col[jp];
+        L.row_of_col[j] = row;
+        L.col[row] = j;
+        j = jp;
+      }
+    }
+    wave_sync();
+  }
+  // the score: D_k by the lanes into the freed u, v, minv; the sums in index order in every lane
+  for (int k = lane; k < n; k += 64) {
+    float D[3];
+    (void)pair_cost(L.y, L.col[k], s_r[k], g, D);
+    L.u[k] = D[0], L.v[k] = D[1], L.minv[k] = D[2];
+  }
+  wave_sync();
+  float sum[3] = {0.f, 0.f, 0.f};
+  for (int k = 0; k < n; ++k) sum[0] += L.u[k], sum[1] += L.v[k], sum[2] += L.minv[k];
+  const float fn = (float)n;
+  const float mean[3] = {sum[0] / fn, sum[1] / fn, sum[2] / fn};
+  float sumq = 0.f, mq = 0.f;
+  for (int k = 0; k < n; ++k) {
+    const float e[3] = {L.u[k] - mean[0], L.v[k] - mean[1], L.minv[k] - mean[2]};
+    const float q = norm2(g, e);
+    sumq += q;
+    mq = fmaxf(mq, q);
+  }
+  *rms = sqrtf(sumq / fn) / ell;
+  *maxq = mq;
+  return true;
+}
+
 // LDS integers of the block
 enum { I_COMP = 0, I_MINCNT, I_PTYPE, I_PREF, I_VOLOK, I_NSURV, I_COUNT };
 // LDS floats of the block
@@ -173,8 +338,11 @@ enum { F_SCALE = 0, F_ELL, F_MAXD, F_COUNT };
 
 // One block (four waves) = sample crystal g against reference r. kPairs = false is k_match (the record of 64
 // bytes at oi, the pairing in p.perm); kPairs = true is k_match_pairs, where both sides come from one state: the
-// compact record {rms, max_dist, flags, matched} at oi[0] and, on a match, `bit` or-ed into *bit_word.
-template <bool kPairs>
+// compact record {rms, max_dist, flags, matched} at oi[0] and, on a match, `bit` or-ed into *bit_word. kAssign =
+// true is the pairing CHM_MATCH_PAIRING_ASSIGNMENT: phase A (a thread per candidate) scores the candidates whose
+// nearest partners are all different and marks the others in a bitmap, phase B (a wave per marked candidate, the
+// lowest kMaxAssign of them) solves their assignment. kAssign = false holds none of that.
+template <bool kPairs, bool kAssign>
 __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, const int r, int4* oi, unsigned* bit_word,
                                             unsigned bit) {
   __shared__ Atom s_s[kMaxAtoms];  // the sample
@@ -185,7 +353,21 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
   __shared__ float s_Ls[9], s_Lr[9], s_f[F_COUNT];
   __shared__ int s_i[I_COUNT], s_wcnt[kBlock / 64];
   __shared__ unsigned long long s_best;
+  unsigned* s_bits = nullptr;  // kAssign: bit `cand` = candidate cand is alive and its nearest partners collide
+  int* s_list = nullptr;       // kAssign: the lowest marked candidates, ascending
+  int* s_nmark = nullptr;      // kAssign: how many are marked
+  AssignLds asg = {};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (kAssign) {
+    __shared__ unsigned a_bits[kBitWords];
+    __shared__ float a_f[kBlock / 64][6 * kMaxAtoms];
+    __shared__ int a_i[kBlock / 64][2 * kMaxAtoms];
+    __shared__ int a_list[kMaxAssign], a_nmark;
+    s_bits = a_bits, s_list = a_list, s_nmark = &a_nmark;
+    asg.y = a_f[wave], asg.u = a_f[wave] + 3 * kMaxAtoms, asg.v = asg.u + kMaxAtoms, asg.minv = asg.v + kMaxAtoms;
+    asg.way = a_i[wave], asg.row_of_col = a_i[wave] + kMaxAtoms;
+    asg.col = reinterpret_cast<int*>(s_taken) + wave * kMaxAtoms;  // (phase A is over when phase B starts)
+  }
   const int n0 = p.off[g], n = p.off[g + 1] - n0;  // (1 <= n <= kMaxAtoms: chm_match_create)
   // (r, n, nr and everything read from the cell records are the same in every thread: the branches on them are uniform)
   if constexpr (!kPairs) {
@@ -325,6 +507,11 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
   const int total = search ? used * n_piv : 0;  // (<= 256 * 256)
   unsigned long long mine = ~0ull;
   float mine_maxd = 0.f;
+  if constexpr (kAssign) {
+    for (int w = tid; w < (total + 31) / 32; w += kBlock) s_bits[w] = 0u;
+    if (tid == 0) *s_nmark = 0;
+    __syncthreads();
+  }
   for (int cand = tid; cand < total; cand += kBlock) {
     const int w = cand / n_piv, jj = cand - w * n_piv;
     float Minv[9], gm[6], t[3];
@@ -339,6 +526,7 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
     for (int q = 0; q < 8; ++q) s_taken[q * kBlock + tid] = 0u;
     float sum[3] = {0.f, 0.f, 0.f};
     bool ok = true;
+    bool collided = false;  // (kAssign only)
     for (int k = 0; k < n && ok; ++k) {
       float best, D[3];
       const int bi = nearest(s_s, n, s_r[k], Minv, t, gm, &best, D);
@@ -348,7 +536,7 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
         const unsigned bit = 1u << (bi & 31);
         const unsigned word = s_taken[(bi >> 5) * kBlock + tid];
         if (word & bit) {
-          ok = false;
+          if constexpr (kAssign) collided = true; else ok = false;  // (the prefilter goes on over the other k)
         } else {
           s_taken[(bi >> 5) * kBlock + tid] = word | bit;
           sum[0] += D[0], sum[1] += D[1], sum[2] += D[2];
@@ -357,6 +545,12 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
     }
     if (!ok) continue;
     atomicAdd(&s_i[I_NSURV], 1);
+    if constexpr (kAssign) {
+      if (collided) {
+        atomicOr(&s_bits[cand >> 5], 1u << (cand & 31));
+        continue;
+      }
+    }
     const float fn = (float)n;
     const float mean[3] = {sum[0] / fn, sum[1] / fn, sum[2] / fn};
     float sumq = 0.f, maxq = 0.f;
@@ -375,6 +569,52 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
       if (key < mine) mine = key, mine_maxd = sqrtf(maxq);
     }
   }
+  int n_assigned = 0;
+  if constexpr (kAssign) {
+    __syncthreads();  // (the bitmap is whole; s_taken is free)
+    // the marked candidates in ascending order: wave 0 ranks the set bits, 64 words a pass
+    if (wave == 0) {
+      const int nwords = (total + 31) / 32;
+      int found = 0;
+      for (int base = 0; base < nwords; base += 64) {
+        const int wi = base + lane;
+        unsigned word = wi < nwords ? s_bits[wi] : 0u;
+        const int cnt = __popc(word);
+        int incl = cnt;
+        for (int d = 1; d < 64; d <<= 1) {
+          const int up = __shfl_up(incl, d, 64);
+          if (lane >= d) incl += up;
+        }
+        int at = found + incl - cnt;
+        while (word != 0u && at < kMaxAssign) {  // (at most 32 turns: one bit leaves the word in each)
+          s_list[at++] = wi * 32 + (__ffs(word) - 1);
+          word &= word - 1u;
+        }
+        found += __shfl(incl, 63, 64);
+      }
+      if (lane == 0) *s_nmark = found;
+    }
+    __syncthreads();
+    const int n_marked = *s_nmark;
+    if (n_marked > kMaxAssign) flags |= CHM_MATCH_MANY_ASSIGNMENTS;
+    n_assigned = n_marked < kMaxAssign ? n_marked : kMaxAssign;
+    // ---- phase B: wave w solves the marked candidates of rank w, w + 4, ...
+    for (int q = wave; q < n_assigned; q += kBlock / 64) {
+      const int cand = s_list[q];
+      const int w = cand / n_piv, jj = cand - w * n_piv;
+      float Minv[9], gm[6], t[3], xj[3], rms, maxq;
+      mapping_frame(s_map[w], sL, gr, Minv, gm);
+      mapped(Minv, s_s[s_piv[jj]].x, xj);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = xj[k] - s_r[pref].x[k];
+      if (!assign_solve(s_s, s_r, n, Minv, t, gm, asg, lane, ell, &rms, &maxq)) continue;
+      if (lane == 0 && rms <= p.stol) {
+        const unsigned long long key =
+            ((unsigned long long)(__float_as_uint(rms) & 0x7fffffffu) << 32) | ((unsigned long long)w << 8) | (unsigned long long)jj;
+        if (key < mine) mine = key, mine_maxd = sqrtf(maxq);
+      }
+    }
+  }
   if (mine != ~0ull) atomicMin(&s_best, mine);
   __syncthreads();
   const unsigned long long best_key = s_best;
@@ -385,7 +625,25 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
   // ---- the winner's pairing, recomputed: reference atom k -> its sample atom
   if (!kPairs && p.perm) {
     int partner = -1;
-    if (matched && tid < n) {
+    bool solved = false;  // (uniform) kAssign: the winner was a collided candidate and wave 0 solves it again
+    if constexpr (kAssign) {
+      const int cand = win_w * n_piv + win_jj;
+      solved = matched && ((s_bits[cand >> 5] >> (cand & 31)) & 1u);
+      if (solved) {
+        __syncthreads();  // (every wave has left phase B: wave 0's slice is free)
+        if (wave == 0) {
+          float Minv[9], gm[6], t[3], xj[3], rms, maxq;
+          mapping_frame(s_map[win_w], sL, gr, Minv, gm);
+          mapped(Minv, s_s[s_piv[win_jj]].x, xj);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) t[k] = xj[k] - s_r[pref].x[k];
+          (void)assign_solve(s_s, s_r, n, Minv, t, gm, asg, lane, ell, &rms, &maxq);
+        }
+        __syncthreads();
+        if (tid < n) partner = reinterpret_cast<const int*>(s_taken)[tid];  // (wave 0's col)
+      }
+    }
+    if (!solved && matched && tid < n) {
       float Minv[9], gm[6], t[3], xj[3], best, D[3];
       mapping_frame(s_map[win_w], sL, gr, Minv, gm);
       mapped(Minv, s_s[s_piv[win_jj]].x, xj);
@@ -399,6 +657,7 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
   if (tid != 0) return;
   const float rms = matched ? __uint_as_float((unsigned)(best_key >> 32)) : 0.f;
   if constexpr (kPairs) {
+    if constexpr (kAssign) flags |= n_assigned << CHM_MATCH_PAIR_ASSIGNED_SHIFT;
     oi[0] = make_int4(__float_as_int(rms), __float_as_int(matched ? s_f[F_MAXD] : 0.f), flags, matched ? 1 : 0);
     if (matched) atomicOr(bit_word, bit);
     return;
@@ -408,14 +667,17 @@ __device__ __forceinline__ void match_block(const MatchArgs& p, const int g, con
                     __float_as_int(frames ? ell : 0.f));
   oi[1] = make_int4(matched ? s_map[win_w] : -1, matched ? s_piv[win_jj] : -1, n_maps, total);
   oi[2] = make_int4(s_i[I_NSURV], matched ? 1 : 0, flags, r);
-  oi[3] = make_int4(0, 0, 0, 0);
+  oi[3] = make_int4(n_assigned, 0, 0, 0);
 }
 
 // Block g = crystal g against reference ref_of[g] (-1 <= ref_of[g] < R: chm_match_create).
-__global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) {
+template <bool kAssign>
+__device__ __forceinline__ void match_body(const MatchArgs& p) {
   const int g = blockIdx.x;
-  match_block<false>(p, g, p.ref_of[g], p.out + 4 * (long)g, nullptr, 0u);
+  match_block<false, kAssign>(p, g, p.ref_of[g], p.out + 4 * (long)g, nullptr, 0u);
 }
+__global__ __launch_bounds__(kBlock) void k_match(MatchArgs p) { match_body<false>(p); }
+__global__ __launch_bounds__(kBlock) void k_match_assign(MatchArgs p) { match_body<true>(p); }
 
 struct PairArgs {
   MatchArgs m;                   // the reference side aliases the sample side; ref_of, out and perm are unused
@@ -427,7 +689,8 @@ struct PairArgs {
 };
 
 // Block b = pair (h, g) = pairs[b]: crystal g as the sample against crystal h as the reference, both of one state.
-__global__ __launch_bounds__(kBlock) void k_match_pairs(PairArgs q) {
+template <bool kAssign>
+__device__ __forceinline__ void match_pairs_body(const PairArgs& q) {
   const int2 pr = q.pairs[blockIdx.x];
   const int h = pr.x, g = pr.y;  // (0 <= h < g < B: chm_match_group_create)
   int4* oi = q.pout + blockIdx.x;
@@ -439,8 +702,10 @@ __global__ __launch_bounds__(kBlock) void k_match_pairs(PairArgs q) {
     if (threadIdx.x == 0) oi[0] = make_int4(0, 0, early, 0);
     return;
   }
-  match_block<true>(q.m, g, h, oi, q.bits + (long)h * q.W + (g >> 5), 1u << (g & 31));
+  match_block<true, kAssign>(q.m, g, h, oi, q.bits + (long)h * q.W + (g >> 5), 1u << (g & 31));
 }
+__global__ __launch_bounds__(kBlock) void k_match_pairs(PairArgs q) { match_pairs_body<false>(q); }
+__global__ __launch_bounds__(kBlock) void k_match_pairs_assign(PairArgs q) { match_pairs_body<true>(q); }
 
 struct GroupArgs {
   int B;
@@ -537,13 +802,23 @@ extern "C" void chm_match_destroy(chm_match* p) {
   delete p;
 }
 
-extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, size_t n_record_bytes,
-                             const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
-                             const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
-                             size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
-                             const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
-                             int64_t n_ref_lattices, float ltol, float stol, float angle_tol, void* d_out,
-                             size_t n_out_bytes, int32_t* d_perm, int64_t n_perm, void* stream) {
+namespace {
+int check_pairing(int pairing) {
+  if (pairing == CHM_MATCH_PAIRING_NEAREST || pairing == CHM_MATCH_PAIRING_ASSIGNMENT) return CHM_OK;
+  return fail(CHM_E_ARG, "pairing = " + std::to_string(pairing) + ": neither CHM_MATCH_PAIRING_NEAREST (0) nor "
+                         "CHM_MATCH_PAIRING_ASSIGNMENT (1)");
+}
+}  // namespace
+
+extern "C" int chm_match_run_pairing(const chm_match* p, const void* d_cell_records, size_t n_record_bytes,
+                                     const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                                     int64_t n_frac, const float* d_lattices, int64_t n_lattices,
+                                     const void* d_ref_cell_records, size_t n_ref_record_bytes,
+                                     const int64_t* d_ref_atom_types, int64_t n_ref_atom_types, const float* d_ref_frac,
+                                     int64_t n_ref_frac, const float* d_ref_lattices, int64_t n_ref_lattices, float ltol,
+                                     float stol, float angle_tol, void* d_out, size_t n_out_bytes, int32_t* d_perm,
+                                     int64_t n_perm, void* stream, int pairing) {
+  if (int rc = check_pairing(pairing)) return rc;
   if (!p) return fail(CHM_E_ARG, "match plan is NULL");
   int rc;
   if ((rc = check.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
@@ -579,9 +854,25 @@ extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, siz
   a.angle_tol = angle_tol;
   a.out = static_cast<int4*>(d_out);
   a.perm = d_perm;
-  hipLaunchKernelGGL(k_match, dim3(p->B), dim3(kBlock), 0, (hipStream_t)stream, a);
+  if (pairing == CHM_MATCH_PAIRING_ASSIGNMENT)
+    hipLaunchKernelGGL(k_match_assign, dim3(p->B), dim3(kBlock), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(k_match, dim3(p->B), dim3(kBlock), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return CHM_OK;
+}
+
+extern "C" int chm_match_run(const chm_match* p, const void* d_cell_records, size_t n_record_bytes,
+                             const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                             const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                             size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                             const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                             int64_t n_ref_lattices, float ltol, float stol, float angle_tol, void* d_out,
+                             size_t n_out_bytes, int32_t* d_perm, int64_t n_perm, void* stream) {
+  return chm_match_run_pairing(p, d_cell_records, n_record_bytes, d_atom_types, n_atom_types, d_frac, n_frac, d_lattices,
+                               n_lattices, d_ref_cell_records, n_ref_record_bytes, d_ref_atom_types, n_ref_atom_types,
+                               d_ref_frac, n_ref_frac, d_ref_lattices, n_ref_lattices, ltol, stol, angle_tol, d_out,
+                               n_out_bytes, d_perm, n_perm, stream, CHM_MATCH_PAIRING_NEAREST);
 }
 
 // ---- grouping a batch by pairwise matching (chm_match_group_*): k_match_pairs over the plan's pair table into the
@@ -662,13 +953,15 @@ extern "C" size_t chm_match_group_workspace_bytes(const chm_match_group* p) {
   return group_bits_bytes(p->B) + 2 * (size_t)p->B * sizeof(int);
 }
 
-extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_records, size_t n_record_bytes,
-                                   const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
-                                   int64_t n_frac, const float* d_lattices, int64_t n_lattices,
-                                   const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol, float angle_tol,
-                                   int32_t* d_group, int64_t n_group, int32_t* d_count, int64_t n_count, void* d_out,
-                                   size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
-                                   size_t workspace_bytes, void* stream) {
+extern "C" int chm_match_group_run_pairing(const chm_match_group* p, const void* d_cell_records, size_t n_record_bytes,
+                                           const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                                           int64_t n_frac, const float* d_lattices, int64_t n_lattices,
+                                           const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol,
+                                           float angle_tol, int32_t* d_group, int64_t n_group, int32_t* d_count,
+                                           int64_t n_count, void* d_out, size_t n_out_bytes, void* d_pair_records,
+                                           size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes, void* stream,
+                                           int pairing) {
+  if (int rc = check_pairing(pairing)) return rc;
   if (!p) return fail(CHM_E_ARG, "match-group plan is NULL");
   int rc;
   if ((rc = check.count(d_cell_records, (long)n_record_bytes, 128L * p->B, "cell records", "bytes"))) return rc;
@@ -731,13 +1024,29 @@ extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_
     a.bits = bits;
     a.W = W;
     a.pout = static_cast<int4*>(d_pair_records);
-    hipLaunchKernelGGL(k_match_pairs, dim3((unsigned)p->P), dim3(kBlock), 0, s, a);
+    if (pairing == CHM_MATCH_PAIRING_ASSIGNMENT)
+      hipLaunchKernelGGL(k_match_pairs_assign, dim3((unsigned)p->P), dim3(kBlock), 0, s, a);
+    else
+      hipLaunchKernelGGL(k_match_pairs, dim3((unsigned)p->P), dim3(kBlock), 0, s, a);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(chm::dedup_lead(B, W, bits, nocell, d_exclude, reps, d_group, d_count, s));
   hipLaunchKernelGGL(k_match_group_gather, per_crystal, dim3(kBlock), 0, s, ga);
   HIPCHK(hipGetLastError());
   return CHM_OK;
+}
+
+extern "C" int chm_match_group_run(const chm_match_group* p, const void* d_cell_records, size_t n_record_bytes,
+                                   const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                                   int64_t n_frac, const float* d_lattices, int64_t n_lattices,
+                                   const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol, float angle_tol,
+                                   int32_t* d_group, int64_t n_group, int32_t* d_count, int64_t n_count, void* d_out,
+                                   size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
+                                   size_t workspace_bytes, void* stream) {
+  return chm_match_group_run_pairing(p, d_cell_records, n_record_bytes, d_atom_types, n_atom_types, d_frac, n_frac,
+                                     d_lattices, n_lattices, d_exclude, n_exclude, ltol, stol, angle_tol, d_group, n_group,
+                                     d_count, n_count, d_out, n_out_bytes, d_pair_records, n_pair_bytes, d_workspace,
+                                     workspace_bytes, stream, CHM_MATCH_PAIRING_NEAREST);
 }
 
 // ---- searching a reference set for each sample (chm_match_set_*): k_set_keys finds each sample's candidates in the
@@ -854,7 +1163,8 @@ struct SetPairArgs {
 // The blocks stride over the pairs b < P of this run: pair b is sample g = the last one with first[g] <= b against
 // the set's sorted position lo[g] + b - first[g]. The record at b depends on the two structures alone; a match adds
 // one to the sample's count and takes the integer minimum of (rms bits, original index) into its winner word.
-__global__ __launch_bounds__(kBlock) void k_set_pairs(SetPairArgs q) {
+template <bool kAssign>
+__device__ __forceinline__ void set_pairs_body(const SetPairArgs& q) {
   const int P = q.first[q.B];
   for (int b = blockIdx.x; b < P; b += gridDim.x) {  // (b and everything derived from it are uniform over the block)
     int g = 0, hi = q.B - 1;  // first[g] <= b < first[hi + 1]
@@ -864,7 +1174,7 @@ __global__ __launch_bounds__(kBlock) void k_set_pairs(SetPairArgs q) {
     }
     const int pos = q.lo[g] + (b - q.first[g]);
     int4* oi = q.pout + b;
-    match_block<true>(q.m, g, pos, oi, q.sink, 0u);
+    match_block<true, kAssign>(q.m, g, pos, oi, q.sink, 0u);
     if (threadIdx.x == 0) {
       const int4 r = oi[0];
       if (r.w) {
@@ -875,6 +1185,8 @@ __global__ __launch_bounds__(kBlock) void k_set_pairs(SetPairArgs q) {
     __syncthreads();  // (thread 0 has read the block's LDS before the next pair is staged)
   }
 }
+__global__ __launch_bounds__(kBlock) void k_set_pairs(SetPairArgs q) { set_pairs_body<false>(q); }
+__global__ __launch_bounds__(kBlock) void k_set_pairs_assign(SetPairArgs q) { set_pairs_body<true>(q); }
 
 // Thread g: the record of sample g against its winner.
 __global__ __launch_bounds__(kBlock) void k_set_gather(SetArgs p) {
@@ -999,14 +1311,17 @@ extern "C" size_t chm_match_set_workspace_bytes(const chm_match_set* p) {
   return align16(2 * (size_t)p->B * sizeof(unsigned long long) + (4 * (size_t)p->B + 2) * sizeof(int));
 }
 
-extern "C" int chm_match_set_run(const chm_match_set* p, const void* d_cell_records, size_t n_record_bytes,
-                                 const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
-                                 const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
-                                 size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
-                                 const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
-                                 int64_t n_ref_lattices, const uint8_t* d_exclude, int64_t n_exclude, float ltol,
-                                 float stol, float angle_tol, void* d_out, size_t n_out_bytes, void* d_pair_records,
-                                 size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chm_match_set_run_pairing(const chm_match_set* p, const void* d_cell_records, size_t n_record_bytes,
+                                         const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac,
+                                         int64_t n_frac, const float* d_lattices, int64_t n_lattices,
+                                         const void* d_ref_cell_records, size_t n_ref_record_bytes,
+                                         const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                                         const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                                         int64_t n_ref_lattices, const uint8_t* d_exclude, int64_t n_exclude, float ltol,
+                                         float stol, float angle_tol, void* d_out, size_t n_out_bytes,
+                                         void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
+                                         size_t workspace_bytes, void* stream, int pairing) {
+  if (int rc = check_pairing(pairing)) return rc;
   if (!p) return fail(CHM_E_ARG, "match-set plan is NULL");
   const chm::Check& check = set_check;
   int rc;
@@ -1084,10 +1399,28 @@ extern "C" int chm_match_set_run(const chm_match_set* p, const void* d_cell_reco
     q.n_matched = a.n_matched;
     q.win = a.win;
     q.sink = reinterpret_cast<unsigned*>(a.first + B + 1);
-    hipLaunchKernelGGL(k_set_pairs, dim3((unsigned)p->grid), dim3(kBlock), 0, s, q);
+    if (pairing == CHM_MATCH_PAIRING_ASSIGNMENT)
+      hipLaunchKernelGGL(k_set_pairs_assign, dim3((unsigned)p->grid), dim3(kBlock), 0, s, q);
+    else
+      hipLaunchKernelGGL(k_set_pairs, dim3((unsigned)p->grid), dim3(kBlock), 0, s, q);
     HIPCHK(hipGetLastError());
   }
   hipLaunchKernelGGL(k_set_gather, dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
   HIPCHK(hipGetLastError());
   return CHM_OK;
+}
+
+extern "C" int chm_match_set_run(const chm_match_set* p, const void* d_cell_records, size_t n_record_bytes,
+                                 const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                                 const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                                 size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                                 const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                                 int64_t n_ref_lattices, const uint8_t* d_exclude, int64_t n_exclude, float ltol,
+                                 float stol, float angle_tol, void* d_out, size_t n_out_bytes, void* d_pair_records,
+                                 size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return chm_match_set_run_pairing(p, d_cell_records, n_record_bytes, d_atom_types, n_atom_types, d_frac, n_frac,
+                                   d_lattices, n_lattices, d_ref_cell_records, n_ref_record_bytes, d_ref_atom_types,
+                                   n_ref_atom_types, d_ref_frac, n_ref_frac, d_ref_lattices, n_ref_lattices, d_exclude,
+                                   n_exclude, ltol, stol, angle_tol, d_out, n_out_bytes, d_pair_records, n_pair_bytes,
+                                   d_workspace, workspace_bytes, stream, CHM_MATCH_PAIRING_NEAREST);
 }

@@ -21,8 +21,11 @@ the smallest rms displacement (mean removed, in units of l) is the answer. The d
 
 This is not a port of pymatgen, and how far the two agree (StructureMatcher.fit) has not been measured. Atom
 counts must be equal: there is no reduction to a primitive cell, so a supercell does not match its primitive
-reference (chemeleon_amd.primitive, primitive_states or sample(primitive=...), is the way round it: it runs first);
-the pairing is the nearest-partner rule, not an optimal assignment ("Matching a reference").
+reference (chemeleon_amd.primitive, primitive_states or sample(primitive=...), is the way round it: it runs first).
+The pairing is the nearest-partner rule by default; Match(..., pairing="assignment") pairs the atoms of a candidate
+whose nearest partners collide by the optimal assignment on the squared distances instead, as StructureMatcher does
+("Matching a reference" and "Pairing by assignment"); at most 64 such candidates per crystal are
+solved (flag many_assignments beyond that) and `n_assigned` says how many were.
 """
 
 import threading
@@ -36,8 +39,21 @@ from chemeleon_amd import cell as _cell
 from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state, hip_device, int32_array
 
 NO_REFERENCE, NO_LATTICE, SIZE, COMPOSITION, THIN, MANY_MAPPINGS = 1, 2, 4, 8, 16, 32
+MANY_ASSIGNMENTS = 128
 FLAG_NAMES = {NO_REFERENCE: "no_reference", NO_LATTICE: "no_lattice", SIZE: "size", COMPOSITION: "composition",
-              THIN: "thin", MANY_MAPPINGS: "many_mappings"}
+              THIN: "thin", MANY_MAPPINGS: "many_mappings", MANY_ASSIGNMENTS: "many_assignments"}
+PAIRINGS = {"nearest": 0, "assignment": 1}  # CHM_MATCH_PAIRING_*
+MAX_ASSIGN = 64
+PAIR_FLAG_BITS = 0xffff    # a pair record's flags word: the CHM_MATCH_* bits ...
+PAIR_ASSIGNED_SHIFT = 16   # ... and n_assigned above them (assignment pairing only)
+
+
+def check_pairing(pairing) -> str:
+    """`pairing` if it is "nearest" or "assignment"; ValueError otherwise."""
+    if not isinstance(pairing, str) or pairing not in PAIRINGS:
+        raise ValueError(f"pairing must be 'nearest' or 'assignment', got {pairing!r}")
+    return pairing
+
 RECORD_BYTES = 64
 MAX_ATOMS = 256
 MAX_MAPPINGS = 256
@@ -113,12 +129,15 @@ class Match:
     -1 for none; None = the one reference for every crystal, or crystal g against reference g when there are as
     many references as crystals), the tolerances `ltol` (relative length, at most 1), `stol` (fraction of
     (V / n)^(1/3), at most 1) and `angle_tol` (degrees, at most 30), and `require`: with True the crystals that do
-    not match count as failed in sample() / finish_atoms. Everything is validated here, on the host (ValueError)."""
+    not match count as failed in sample() / finish_atoms; `pairing`: "nearest" (each reference atom takes its nearest
+    sample atom, a candidate with a collision is given up) or "assignment" (a collided candidate is paired by the
+    optimal assignment). Everything is validated here, on the host (ValueError)."""
 
     def __init__(self, reference: Reference, ref_of: Optional[Sequence[int]] = None, ltol: float = 0.2,
-                 stol: float = 0.3, angle_tol: float = 5.0, require: bool = False):
+                 stol: float = 0.3, angle_tol: float = 5.0, require: bool = False, pairing: str = "nearest"):
         if not isinstance(reference, Reference):
             raise ValueError("reference must be a chemeleon_amd.Reference")
+        self.pairing = check_pairing(pairing)
         for name, v, top in (("ltol", ltol, MAX_LTOL), ("stol", stol, MAX_STOL), ("angle_tol", angle_tol, MAX_ANGLE_TOL)):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
                 raise ValueError(f"{name} must be a number, got {v!r}")
@@ -160,13 +179,13 @@ class Match:
 
     def __repr__(self):
         return (f"Match({len(self.reference)} references, ltol={self.ltol}, stol={self.stol}, angle_tol={self.angle_tol}, "
-                f"require={self.require})")
+                f"require={self.require}" + (f", pairing={self.pairing!r})" if self.pairing != "nearest" else ")"))
 
 
 class MatchReport:
     """The records of one batch as numpy arrays: matched [B] (bool), rms [B] (units of l), max_dist [B] (A), scale
     [B], l [B], mapping [B] (candidate index, -1), anchor [B] (-1), n_mappings, n_candidates, n_survivors [B],
-    flags [B], ref [B]; n_matched, match_rate, rms_mean (over the matched crystals; nan if none), and mismatch [B]
+    flags [B], ref [B], n_assigned [B] (candidates paired by assignment; 0 under "nearest"); n_matched, match_rate, rms_mean (over the matched crystals; nan if none), and mismatch [B]
     (= not matched). `perm` is None or, if asked for, int32 [N]: per crystal, at its node offset, the sample atom
     paired with each reference atom (-1 in a crystal that is not matched)."""
 
@@ -179,6 +198,7 @@ class MatchReport:
         self.n_mappings, self.n_candidates, self.n_survivors = i[:, 6].copy(), i[:, 7].copy(), i[:, 8].copy()
         self.matched = i[:, 9] != 0
         self.flags, self.ref = i[:, 10].copy(), i[:, 11].copy()
+        self.n_assigned = i[:, 12].copy()
         self.mismatch = ~self.matched
         self.n_matched = int(self.matched.sum())
         self.match_rate = self.n_matched / len(rec) if len(rec) else float("nan")
@@ -194,7 +214,7 @@ class MatchReport:
         return {"matched": bool(self.matched[g]), "rms": float(self.rms[g]), "max_dist": float(self.max_dist[g]),
                 "scale": float(self.scale[g]), "l": float(self.l[g]), "mapping": int(self.mapping[g]),
                 "anchor": int(self.anchor[g]), "n_mappings": int(self.n_mappings[g]),
-                "n_candidates": int(self.n_candidates[g]), "n_survivors": int(self.n_survivors[g]), "flags": fl,
+                "n_candidates": int(self.n_candidates[g]), "n_survivors": int(self.n_survivors[g]), "n_assigned": int(self.n_assigned[g]), "flags": fl,
                 "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit], "ref": int(self.ref[g])}
 
 
@@ -213,17 +233,18 @@ class MatchPlan(Plan):
                    int32_array(self.ref_of))
 
     def run(self, cell_records, atom_types, frac_coords, lattices, ref_cell_records, ref_atom_types, ref_frac_coords,
-            ref_lattices, ltol: float, stol: float, angle_tol: float, out, perm=None):
+            ref_lattices, ltol: float, stol: float, angle_tol: float, out, perm=None, pairing: str = "nearest"):
         """Enqueues the search on the current stream of the plan's device: the cell records are the outputs of
         CellPlan.run on the two lattice lists, `out` a uint8 device tensor of 64 bytes per crystal, `perm` None or
         an int32 device tensor [N]. No host wait."""
-        _lib.check(_lib.load().chm_match_run(
+        _lib.check(_lib.load().chm_match_run_pairing(
             self.handle, _lib.ptr(cell_records), cell_records.numel(), _lib.ptr(atom_types), atom_types.numel(),
             _lib.ptr(frac_coords), frac_coords.numel(), _lib.ptr(lattices), lattices.numel(),
             _lib.ptr(ref_cell_records), ref_cell_records.numel(), _lib.ptr(ref_atom_types), ref_atom_types.numel(),
             _lib.ptr(ref_frac_coords), ref_frac_coords.numel(), _lib.ptr(ref_lattices), ref_lattices.numel(),
             float(ltol), float(stol), float(angle_tol), _lib.ptr(out), out.numel(), _lib.ptr(perm),
-            0 if perm is None else perm.numel(), _lib.stream_handle(self.device)), "chm_match_run")
+            0 if perm is None else perm.numel(), _lib.stream_handle(self.device), PAIRINGS[check_pairing(pairing)]),
+            "chm_match_run_pairing")
         return out
 
 
@@ -253,7 +274,7 @@ def match_states(natoms: Sequence[int], atom_types, frac_coords, lattices, match
         pm = torch.empty(N, dtype=torch.int32, device=dev) if perm else None
         cells.run(lattices, None, MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE, cell_rec)
         plan.run(cell_rec, atom_types, frac_coords, lattices, rrec, ra, rx, rlat, match.ltol, match.stol,
-                 match.angle_tol, out, pm)
+                 match.angle_tol, out, pm, match.pairing)
         host = out.cpu().numpy()  # (waits for the kernels; cell_rec and out stay alive until here)
         host_perm = pm.cpu().numpy() if perm else None
     return MatchReport(host, host_perm)

@@ -25,8 +25,10 @@ candidate with the smallest rms (ties: the smallest original index).
 This is not a port of StructureMatcher, and how far known / novel agree with StructureMatcher.fit against every
 structure of the set has not been measured. Atom counts must be equal: there is no reduction to a primitive cell,
 so a supercell is never found to be its primitive cell (chemeleon_amd.primitive, primitive_states or
-sample(primitive=...), is the way round it: it runs first; reduce the set likewise); the pairing is the
-nearest-partner rule, not an optimal assignment ("Searching a reference set").
+sample(primitive=...), is the way round it: it runs first; reduce the set likewise). The pairing is the
+nearest-partner rule by default; MatchSet(..., pairing="assignment") pairs a candidate whose nearest partners collide
+by the optimal assignment instead (chemeleon_amd.match; DESIGN.md §4, "Searching a reference set" and "Pairing by
+assignment").
 """
 
 import itertools
@@ -40,7 +42,8 @@ from chemeleon_amd import _lib
 from chemeleon_amd import cell as _cell
 from chemeleon_amd._plans import Plan, PlanCache, check_natoms, check_state, exclude_tensor, int32_array
 from chemeleon_amd.match import (COMPOSITION, MANY_MAPPINGS, MATCH_CELL_ANGLE_TOLERANCE, MATCH_CELL_SYMPREC, MAX_ANGLE_TOL,
-                                 MAX_ATOMS, MAX_LTOL, MAX_STOL, NO_LATTICE, THIN, Reference)
+                                 MAX_ATOMS, MAX_LTOL, MAX_STOL, NO_LATTICE, PAIR_ASSIGNED_SHIFT, PAIR_FLAG_BITS, PAIRINGS,
+                                 THIN, Reference, check_pairing)
 from chemeleon_amd.match_group import EXCLUDED, FLAG_NAMES, PAIR_RECORD_BYTES
 
 RECORD_BYTES = 48
@@ -108,10 +111,12 @@ class MatchSet:
     """How finished structures are searched for in `reference_set` (a ReferenceSet): the tolerances `ltol` (relative
     length, at most 1), `stol` (fraction of (V / n)^(1/3), at most 1) and `angle_tol` (degrees, at most 30) of each
     match, and `require`: with "known" the structures that are in no way in the set count as failed in sample() /
-    finish_atoms, with "novel" the ones that are. Everything is validated here, on the host (ValueError)."""
+    finish_atoms, with "novel" the ones that are; `pairing` is "nearest" or "assignment" (chemeleon_amd.match.Match).
+    Everything is validated here, on the host (ValueError)."""
 
     def __init__(self, reference_set: ReferenceSet, ltol: float = 0.2, stol: float = 0.3, angle_tol: float = 5.0,
-                 require: Optional[str] = None):
+                 require: Optional[str] = None, pairing: str = "nearest"):
+        self.pairing = check_pairing(pairing)
         if not isinstance(reference_set, ReferenceSet):
             raise ValueError("reference_set must be a chemeleon_amd.ReferenceSet")
         for name, v, top in (("ltol", ltol, MAX_LTOL), ("stol", stol, MAX_STOL), ("angle_tol", angle_tol, MAX_ANGLE_TOL)):
@@ -126,13 +131,15 @@ class MatchSet:
 
     def __repr__(self):
         return (f"MatchSet({len(self.reference_set)} references, ltol={self.ltol}, stol={self.stol}, "
-                f"angle_tol={self.angle_tol}, require={self.require!r})")
+                f"angle_tol={self.angle_tol}, require={self.require!r}" +
+                (f", pairing={self.pairing!r})" if self.pairing != "nearest" else ")"))
 
 
 class MatchSetReport:
     """One search as numpy arrays, per sample: known [B] and novel [B] (bool; an excluded sample or one without a
     reduced cell is neither), ref [B] (the winner's original index, -1), position [B] (its sorted position, -1), rms
-    [B] (units of l of that reference), max_dist [B] (A), n_candidates [B], n_matched [B], key [B] (uint64), flags
+    [B] (units of l of that reference), max_dist [B] (A), n_assigned [B] (candidates of the winner's pair paired by
+    assignment; pair_n_assigned per launched pair), n_candidates [B], n_matched [B], key [B] (uint64), flags
     [B], first [B] and lo [B] (where the sample's pair records and its candidates start); n_known, n_novel,
     novelty_rate (novel over the samples that were searched; nan if none), mismatch [B] according to `require`
     (all False without one); `records` the 48-byte records. Per launched pair, in the order of the samples and of
@@ -144,7 +151,8 @@ class MatchSetReport:
         f, i = rec.view(np.float32), rec.view(np.int32)
         self.records = rec
         self.rms, self.max_dist = f[:, 0].copy(), f[:, 1].copy()
-        self.flags, self.known = i[:, 2].copy(), i[:, 3] != 0
+        self.flags, self.known = i[:, 2] & PAIR_FLAG_BITS, i[:, 3] != 0
+        self.n_assigned = i[:, 2] >> PAIR_ASSIGNED_SHIFT
         self.ref, self.position = i[:, 4].copy(), i[:, 5].copy()
         self.n_candidates, self.n_matched = i[:, 6].copy(), i[:, 7].copy()
         self.key = rec.view(np.uint64)[:, 4].copy()
@@ -167,7 +175,8 @@ class MatchSetReport:
         self.pair_ref = self.order[np.repeat(self.lo.astype(np.int64), self.n_candidates) + within] if P else \
             np.zeros(0, dtype=np.int32)
         self.pair_rms, self.pair_max_dist = pf[:, 0].copy(), pf[:, 1].copy()
-        self.pair_flags, self.pair_matched = pi[:, 2].copy(), pi[:, 3] != 0
+        self.pair_flags, self.pair_matched = pi[:, 2] & PAIR_FLAG_BITS, pi[:, 3] != 0
+        self.pair_n_assigned = pi[:, 2] >> PAIR_ASSIGNED_SHIFT
 
     def __len__(self):
         return len(self.flags)
@@ -182,7 +191,8 @@ class MatchSetReport:
         fl = int(self.flags[g])
         return {"known": bool(self.known[g]), "novel": bool(self.novel[g]), "ref": int(self.ref[g]),
                 "rms": float(self.rms[g]), "max_dist": float(self.max_dist[g]), "n_candidates": int(self.n_candidates[g]),
-                "n_matched": int(self.n_matched[g]), "key": int(self.key[g]), "flags": fl,
+                "n_matched": int(self.n_matched[g]), "n_assigned": int(self.n_assigned[g]), "key": int(self.key[g]),
+                "flags": fl,
                 "failed": [name for bit, name in FLAG_NAMES.items() if fl & bit]}
 
 
@@ -205,19 +215,21 @@ class MatchSetPlan(Plan):
         self.workspace_bytes = int(lib.chm_match_set_workspace_bytes(self.handle))
 
     def run(self, cell_records, atom_types, frac_coords, lattices, ref_cell_records, ref_atom_types, ref_frac_coords,
-            ref_lattices, exclude, ltol: float, stol: float, angle_tol: float, out, pair_records, workspace):
+            ref_lattices, exclude, ltol: float, stol: float, angle_tol: float, out, pair_records, workspace,
+            pairing: str = "nearest"):
         """Enqueues the search on the current stream of the plan's device: the cell records are the outputs of
         CellPlan.run on the two lattice lists (the references in sorted order), `exclude` None or a uint8 device
         tensor [B], `out` uint8 of 48 bytes per crystal, `pair_records` uint8 of 16 bytes x num_pairs_max (None when
         that is 0), `workspace` uint8 of at least workspace_bytes. No host wait."""
-        _lib.check(_lib.load().chm_match_set_run(
+        _lib.check(_lib.load().chm_match_set_run_pairing(
             self.handle, _lib.ptr(cell_records), cell_records.numel(), _lib.ptr(atom_types), atom_types.numel(),
             _lib.ptr(frac_coords), frac_coords.numel(), _lib.ptr(lattices), lattices.numel(),
             _lib.ptr(ref_cell_records), ref_cell_records.numel(), _lib.ptr(ref_atom_types), ref_atom_types.numel(),
             _lib.ptr(ref_frac_coords), ref_frac_coords.numel(), _lib.ptr(ref_lattices), ref_lattices.numel(),
             _lib.ptr(exclude), 0 if exclude is None else exclude.numel(), float(ltol), float(stol), float(angle_tol),
             _lib.ptr(out), out.numel(), _lib.ptr(pair_records), 0 if pair_records is None else pair_records.numel(),
-            _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device)), "chm_match_set_run")
+            _lib.ptr(workspace), workspace.numel(), _lib.stream_handle(self.device), PAIRINGS[check_pairing(pairing)]),
+            "chm_match_set_run_pairing")
 
 
 _plans = PlanCache(lambda natoms, token, device: MatchSetPlan(natoms, _sets[token[0]], device))
@@ -253,7 +265,7 @@ def match_set_states(natoms: Sequence[int], atom_types, frac_coords, lattices, m
         ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=dev)
         cells.run(lattices, None, MATCH_CELL_SYMPREC, MATCH_CELL_ANGLE_TOLERANCE, cell_rec)
         plan.run(cell_rec, atom_types, frac_coords, lattices, rrec, ra, rx, rlat, ex, match_set.ltol, match_set.stol,
-                 match_set.angle_tol, out, pair_rec, ws)
+                 match_set.angle_tol, out, pair_rec, ws, match_set.pairing)
         host = out.cpu().numpy()  # (waits for the kernels; every buffer stays alive until here)
         P = int(host.view(np.int32).reshape(B, -1)[:, 6].sum())
         host_pairs = pair_rec[:P * PAIR_RECORD_BYTES].cpu().numpy() if P else np.zeros(0, dtype=np.uint8)

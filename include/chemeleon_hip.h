@@ -1094,7 +1094,28 @@ int chm_prim_run(const chm_prim* plan, const void* d_cell_records, size_t n_reco
  * with the smallest |D|^2, D = (y_i - xr_k) - rintf(y_i - xr_k) per component (one image per component; ties go
  * to the smallest i). The candidate is given up at the first k whose partner has |D|^2 > c^2 (or not <=) or was
  * taken by an earlier k. A candidate that pairs every k survives: the pairing is a type-preserving bijection.
- * This is a nearest-partner rule, not pymatgen's optimal assignment.
+ * This is a nearest-partner rule, not pymatgen's optimal assignment; it is pairing CHM_MATCH_PAIRING_NEAREST, the
+ * only one of chm_match_run / chm_match_group_run / chm_match_set_run.
+ *
+ * Pairing of a candidate (M, j) by assignment (CHM_MATCH_PAIRING_ASSIGNMENT, the *_run_pairing entry points; what
+ * pymatgen's _cart_dists does with a linear assignment on the squared distances). Frames, scale, l, mappings,
+ * anchors, metric, the thin-cell rule and the arithmetic rule are the ones of this text. (1) Prefilter: the
+ * candidate stays alive when every reference atom k has a sample atom of its type with |D|^2 <= c^2; it is given
+ * up at the first k with !(best <= c^2), which also removes NaN. n_survivors counts the alive candidates. (2) If
+ * the nearest partners of an alive candidate are all different, that pairing is the optimum (the sum of the row
+ * minima is a lower bound of every bijection's sum) and it is scored by the code of the nearest rule: its rms has
+ * the same bits. (3) Otherwise the pairing is the type-preserving bijection that minimises sum_k |D_k|^2, D the
+ * same one-image-per-component vector, over all sample atoms of the type (only the prefilter uses c). It is found
+ * per species by shortest augmenting paths in fp32: duals u_k = min_i |D(k, i)|^2 (ties: the smallest i) and v =
+ * 0; a column keeps the smallest row that wants it; every other row, in ascending k, grows a tree from reduced
+ * costs (|D|^2 - u_k) - v_i, the next column being the one of smallest reduced cost (ties: the smallest i), until
+ * a free column is reached. Every loop is bounded by n; a row that finds no column (NaN or Inf) ends the
+ * candidate, which then does not count. (4) Score, the rms <= stol test and the winner key are unchanged.
+ * At most CHM_MATCH_MAX_ASSIGN (64) collided candidates per crystal are solved, the lowest (mapping position,
+ * anchor position) first; more than that sets CHM_MATCH_MANY_ASSIGNMENTS and the others do not count. n_assigned
+ * = the number solved: the first reserved word of chm_match_record, bits 16..23 of the flags word of a
+ * 16-byte pair record, and of the group / set record that copies it. Under CHM_MATCH_PAIRING_NEAREST those
+ * stay 0 and every byte is what the old entry point writes: pairing 0 enqueues exactly the same kernels.
  *
  * Score of a survivor. m = (sum_k D_k) / n (sums in index order), e_k = D_k - m, rms = sqrtf((sum_k |e_k|^2) /
  * n) / l, max_dist = sqrtf(max_k |e_k|^2) (A). The candidate counts if rms <= stol. matched = 1 if any candidate
@@ -1127,7 +1148,12 @@ int chm_prim_run(const chm_prim* plan, const void* d_cell_records, size_t n_reco
 #define CHM_MATCH_COMPOSITION 8    /* element counts differ */
 #define CHM_MATCH_THIN 16          /* 2 stol l is not below the smallest plane spacing of Lr */
 #define CHM_MATCH_MANY_MAPPINGS 32 /* more than CHM_MATCH_MAX_MAPPINGS accepted: the first ones were used */
+#define CHM_MATCH_MANY_ASSIGNMENTS 128 /* more than CHM_MATCH_MAX_ASSIGN collided candidates: the lowest were solved */
 #define CHM_MATCH_MAX_MAPPINGS 256
+#define CHM_MATCH_MAX_ASSIGN 64
+#define CHM_MATCH_PAIR_ASSIGNED_SHIFT 16 /* chm_match_pair_record.flags: n_assigned << 16 (assignment pairing only) */
+#define CHM_MATCH_PAIRING_NEAREST 0
+#define CHM_MATCH_PAIRING_ASSIGNMENT 1
 #define CHM_MATCH_MAX_LTOL 1.0f
 #define CHM_MATCH_MAX_STOL 1.0f
 #define CHM_MATCH_MAX_ANGLE_TOL 30.0f
@@ -1144,7 +1170,7 @@ typedef struct {
   int32_t matched;            /* 1 or 0 */
   int32_t flags;              /* CHM_MATCH_* bits */
   int32_t ref;                /* ref_of of the crystal */
-  int32_t reserved[4];        /* written as 0 */
+  int32_t reserved[4];        /* written as 0; reserved[0] = n_assigned under CHM_MATCH_PAIRING_ASSIGNMENT */
 } chm_match_record;           /* 64 bytes */
 typedef struct chm_match chm_match;
 int chm_match_create(const int32_t* h_natoms, int num_graphs, const int32_t* h_ref_natoms, int num_refs,
@@ -1157,6 +1183,16 @@ int chm_match_run(const chm_match* plan, const void* d_cell_records, size_t n_re
                   const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices, int64_t n_ref_lattices,
                   float ltol, float stol, float angle_tol, void* d_out, size_t n_out_bytes, int32_t* d_perm,
                   int64_t n_perm, void* stream);
+/* chm_match_run with the pairing chosen: CHM_MATCH_PAIRING_NEAREST (what chm_match_run enqueues, byte for byte) or
+ * CHM_MATCH_PAIRING_ASSIGNMENT; any other value returns CHM_E_ARG before any HIP call. d_perm holds the assignment
+ * where the winner was a collided candidate. */
+int chm_match_run_pairing(const chm_match* plan, const void* d_cell_records, size_t n_record_bytes,
+                          const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                          const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                          size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                          const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                          int64_t n_ref_lattices, float ltol, float stol, float angle_tol, void* d_out,
+                          size_t n_out_bytes, int32_t* d_perm, int64_t n_perm, void* stream, int pairing);
 
 /* Grouping duplicate structures of one batch by pairwise matching on the device: the uniqueness step of the
  * reference's workflows (StructureMatcher().group_structures in test_unique of scripts/evaluate.py and in
@@ -1201,7 +1237,7 @@ int chm_match_run(const chm_match* plan, const void* d_cell_records, size_t n_re
 typedef struct {
   float rms;       /* of the winner, in units of l of crystal h */
   float max_dist;  /* of the winner (A) */
-  int32_t flags;   /* CHM_MATCH_* bits */
+  int32_t flags;   /* CHM_MATCH_* bits; bits 16..23 = n_assigned under CHM_MATCH_PAIRING_ASSIGNMENT */
   int32_t matched; /* 1 or 0 */
 } chm_match_pair_record; /* 16 bytes */
 typedef struct {
@@ -1224,6 +1260,14 @@ int chm_match_group_run(const chm_match_group* plan, const void* d_cell_records,
                         float ltol, float stol, float angle_tol, int32_t* d_group, int64_t n_group, int32_t* d_count,
                         int64_t n_count, void* d_out, size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes,
                         void* d_workspace, size_t workspace_bytes, void* stream);
+/* chm_match_group_run with the pairing chosen (see chm_match_run_pairing). */
+int chm_match_group_run_pairing(const chm_match_group* plan, const void* d_cell_records, size_t n_record_bytes,
+                                const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                                const float* d_lattices, int64_t n_lattices, const uint8_t* d_exclude,
+                                int64_t n_exclude, float ltol, float stol, float angle_tol, int32_t* d_group,
+                                int64_t n_group, int32_t* d_count, int64_t n_count, void* d_out, size_t n_out_bytes,
+                                void* d_pair_records, size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes,
+                                void* stream, int pairing);
 
 /* Searching a set of reference structures for each finished structure on the device: is this sample any structure
  * of the set (known) or none of them (novel)? It is what the users of the reference's
@@ -1231,7 +1275,7 @@ int chm_match_group_run(const chm_match_group* plan, const void* d_cell_records,
  * representatives kept so far) with the match criterion above. This is NOT a port of pymatgen, and how far known /
  * novel agree with StructureMatcher().fit against every structure of the set has not been measured. It inherits
  * every caveat of chm_match_*: atom counts must be equal (no reduction to a primitive cell: chm_prim_* first is the
- * way round it), and the pairing is the nearest-partner rule, not an optimal assignment.
+ * way round it), and the pairing is the nearest-partner rule unless chm_match_set_run_pairing asks for the assignment.
  *
  * Composition key. key = sum_i mix(t_i) over the atoms of a structure, as wrapping 64-bit unsigned addition, where
  * t_i is the atom type's low 32 bits as an unsigned number (what the matcher compares) and mix is the splitmix64
@@ -1309,6 +1353,16 @@ int chm_match_set_run(const chm_match_set* plan, const void* d_cell_records, siz
                       const uint8_t* d_exclude, int64_t n_exclude, float ltol, float stol, float angle_tol, void* d_out,
                       size_t n_out_bytes, void* d_pair_records, size_t n_pair_bytes, void* d_workspace,
                       size_t workspace_bytes, void* stream);
+/* chm_match_set_run with the pairing chosen (see chm_match_run_pairing). The grid is the one chosen at create; the
+ * assignment kernel's LDS lets a CU hold two of its blocks, the others wait their turn. */
+int chm_match_set_run_pairing(const chm_match_set* plan, const void* d_cell_records, size_t n_record_bytes,
+                              const int64_t* d_atom_types, int64_t n_atom_types, const float* d_frac, int64_t n_frac,
+                              const float* d_lattices, int64_t n_lattices, const void* d_ref_cell_records,
+                              size_t n_ref_record_bytes, const int64_t* d_ref_atom_types, int64_t n_ref_atom_types,
+                              const float* d_ref_frac, int64_t n_ref_frac, const float* d_ref_lattices,
+                              int64_t n_ref_lattices, const uint8_t* d_exclude, int64_t n_exclude, float ltol,
+                              float stol, float angle_tol, void* d_out, size_t n_out_bytes, void* d_pair_records,
+                              size_t n_pair_bytes, void* d_workspace, size_t workspace_bytes, void* stream, int pairing);
 
 /* Sizes of the batch (for callers that allocate outputs). */
 int64_t chm_batch_num_nodes(const chm_batch* b);
