@@ -33,6 +33,34 @@ SHAPES = {
     "tiny55": [1] * 40 + [2] * 10 + [3] * 5,
     "ragged5": [23, 7, 40, 1, 80],
 }
+# crystals of 81 to 256 atoms, the rest of the range a fully connected batch accepts (the largest: 71 439 edge rows).
+# A table of its own: the parametrisations over SHAPES do not multiply. 81: the first size above SHAPES; 127 / 128:
+# 64 / 65 pair tiles below the last row tile, one / two passes of the pair grid's flag polling; 193+: above 192 atoms
+# (no 192-row tiles) in a ragged batch; 255: every node cut by a tile edge at another offset; 256: a node's rows are
+# one row tile; ragged256: the batch of tests/test_row_tiles.py.
+BIG_SHAPES = {
+    "81": [81], "127": [127], "128": [128], "193+": [193, 20, 20], "255": [255], "256": [256],
+    "ragged256": [1, 255, 2, 80, 3],
+}
+ALL_SHAPES = {**SHAPES, **BIG_SHAPES}
+# edge rows per block of source nodes in ref64 / base32: every shape of SHAPES is one block, as it always was; a big
+# shape's feature matrix (65 536 x 768) is never allocated whole
+REF_BLOCK_ROWS = 16384
+
+
+def node_blocks(natoms, max_rows=None):
+    """[(first node, end node, first edge row, end edge row)]: consecutive source nodes whose edge rows (a node's
+    rows are contiguous) number at most max_rows (REF_BLOCK_ROWS), one node at the least."""
+    max_rows = REF_BLOCK_ROWS if max_rows is None else max_rows
+    n = node_counts(natoms)
+    end = np.cumsum(n)
+    out, a = [], 0
+    while a < len(n):
+        r0 = int(end[a] - n[a])
+        b = max(a + 1, int(np.searchsorted(end, r0 + max_rows, side="right")))
+        out.append((a, b, r0, int(end[b - 1])))
+        a = b
+    return out
 
 
 def fc_edges(natoms):
@@ -110,40 +138,46 @@ def silu64(x):
 
 
 def ref64(natoms, frac, PQ, w, pairs=False):
-    """agg [P, N, H] float64: float64 from the fp32 arguments on. PQ [P, N, 2H] float32, w = layer_weights()."""
+    """agg [P, N, H] float64: float64 from the fp32 arguments on. PQ [P, N, 2H] float32, w = layer_weights().
+    Computed per block of source nodes (node_blocks)."""
     ei, ej = fc_edges(natoms)
-    arg = fourier_args(frac, ei, ej, pairs).astype(np.float64)
-    DF = np.concatenate([np.sin(arg), np.cos(arg)], 1) @ w["D"].astype(np.float64).T
+    Dt = w["D"].astype(np.float64).T
     PQ = np.asarray(PQ, np.float64)
     W2t, b2 = w["W2"].astype(np.float64).T, w["b2"].astype(np.float64)
     n = node_counts(natoms)
     starts = np.concatenate([[0], np.cumsum(n)[:-1]])
     out = np.empty((PQ.shape[0], len(n), H))
-    for c in range(PQ.shape[0]):
-        S = silu64(DF + PQ[c, ei, :H] + PQ[c, ej, H:])
-        M = silu64(S @ W2t + b2)
-        out[c] = np.add.reduceat(M, starts, axis=0) / n[:, None]
+    for a, b, r0, r1 in node_blocks(natoms):
+        bi, bj = ei[r0:r1], ej[r0:r1]
+        arg = fourier_args(frac, bi, bj, pairs).astype(np.float64)
+        DF = np.concatenate([np.sin(arg), np.cos(arg)], 1) @ Dt
+        for c in range(PQ.shape[0]):
+            S = silu64(DF + PQ[c, bi, :H] + PQ[c, bj, H:])
+            M = silu64(S @ W2t + b2)
+            out[c, a:b] = np.add.reduceat(M, starts[a:b] - r0, axis=0) / n[a:b, None]
     return out
 
 
 def base32(natoms, frac, PQ, w, pairs=False):
     """The same chain in torch float32 on the CPU (the baseline, as baseline_eta is for the GEMMs): sin / cos of the
-    same fp32 arguments, F.linear, F.silu, scatter-add mean. [P, N, H] float32 numpy."""
+    same fp32 arguments, F.linear, F.silu, scatter-add mean, per block of source nodes. [P, N, H] float32 numpy."""
     import torch
     import torch.nn.functional as F
     ei, ej = fc_edges(natoms)
-    arg = torch.from_numpy(fourier_args(frac, ei, ej, pairs))
-    DF = torch.cat([arg.sin(), arg.cos()], 1) @ torch.from_numpy(w["D"]).T
+    Dt = torch.from_numpy(w["D"]).T
     PQ = torch.tensor(np.asarray(PQ, np.float32))
     W2, b2 = torch.from_numpy(w["W2"]), torch.from_numpy(w["b2"])
-    ti, tj = torch.from_numpy(ei), torch.from_numpy(ej)
     n = torch.from_numpy(node_counts(natoms)).float()
-    out = []
-    for c in range(PQ.shape[0]):
-        S = F.silu(DF + PQ[c, ti, :H] + PQ[c, tj, H:])
-        M = F.silu(F.linear(S, W2, b2))
-        out.append(torch.zeros(len(n), H).index_add_(0, ti, M) / n[:, None])
-    return torch.stack(out).numpy()
+    out = torch.empty(PQ.shape[0], len(n), H)
+    for a, b, r0, r1 in node_blocks(natoms):
+        arg = torch.from_numpy(fourier_args(frac, ei[r0:r1], ej[r0:r1], pairs))
+        DF = torch.cat([arg.sin(), arg.cos()], 1) @ Dt
+        ti, tj = torch.from_numpy(ei[r0:r1]), torch.from_numpy(ej[r0:r1])
+        for c in range(PQ.shape[0]):
+            S = F.silu(DF + PQ[c, ti, :H] + PQ[c, tj, H:])
+            M = F.silu(F.linear(S, W2, b2))
+            out[c, a:b] = torch.zeros(b - a, H).index_add_(0, ti - a, M) / n[a:b, None]
+    return out.numpy()
 
 
 def row_errors(agg, ref):

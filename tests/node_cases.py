@@ -25,7 +25,10 @@ from chemeleon_amd.synthetic import synthetic_state_dict
 
 H, TD, HEADS_N, GB_LAYERS = 512, 128, 128, 16
 EPS = 1e-5
-SHAPES = {"1": [1], "123": [1, 2, 3], "unroll": [7, 8, 9, 16, 17], "odd": [5] * 3, "80": [80]}
+# (256 / big_ragged: the largest crystal a fully connected batch takes, alone and between small ones: the loops and
+# reductions over a crystal's atoms at three times the reference workload's 80)
+SHAPES = {"1": [1], "123": [1, 2, 3], "unroll": [7, 8, 9, 16, 17], "odd": [5] * 3, "80": [80],
+          "256": [256], "big_ragged": [1, 255, 2]}
 PAIRS = (1, 2)
 # (a) FiLM, (b) time only with 33 layers (per-graph terms in groups of 16 + 16 + 1), (c) no FilmLayer,
 # (d) = (a) with 1 and 125 atom classes (the tail only: 125 + 3 fills the packed head rows)

@@ -42,7 +42,8 @@ def _decoder_pq(natoms, w, seed):
 
 
 @pytest.mark.parametrize("layer", [0, 5])
-@pytest.mark.parametrize("natoms", [[5, 9, 3, 12, 7, 1, 20], [23, 7, 1, 30]], ids=["mixed7", "ragged4"])
+@pytest.mark.parametrize("natoms", [[5, 9, 3, 12, 7, 1, 20], [23, 7, 1, 30], EC.BIG_SHAPES["81"]],
+                         ids=["mixed7", "ragged4", "81"])
 def test_reference_is_the_oracles_message_path(natoms, layer):
     sd, w = _sd(), EC.layer_weights(_sd(), layer)
     frac, lat, hl, PQ = _decoder_pq(natoms, w, 7 + layer)
@@ -65,7 +66,7 @@ def test_reference_is_the_oracles_message_path(natoms, layer):
 
 
 def test_fc_edges_and_rem1_match_torch():
-    for nat in ([1], [3, 1, 4], EC.SHAPES["ragged5"]):
+    for nat in ([1], [3, 1, 4], EC.SHAPES["ragged5"], *EC.BIG_SHAPES.values()):
         ei, ej = EC.fc_edges(nat)
         e = O.fc_edges(nat).numpy()
         assert np.array_equal(ei, e[0]) and np.array_equal(ej, e[1])
@@ -104,6 +105,59 @@ def test_pair_arguments_are_the_forward_edges_negated():
     # same features in real arithmetic; in fp32 the two argument roundings differ (edge16.hip: up to 8e-5)
     dsin = np.abs(np.sin(a_d.astype(np.float64)) - np.sin(a_p.astype(np.float64))).max()
     assert 0 < dsin < 2e-4
+
+
+def test_big_shapes_are_what_they_are_chosen_for():
+    """The edge rows of each big shape, the sizes that bracket a threshold, and the tables kept apart."""
+    rows = {k: sum(n * n for n in v) for k, v in EC.BIG_SHAPES.items()}
+    assert rows == {"81": 6561, "127": 16129, "128": 16384, "193+": 38049, "255": 65025, "256": 65536,
+                    "ragged256": 71439}
+    assert not set(EC.BIG_SHAPES) & set(EC.SHAPES) and len(EC.ALL_SHAPES) == len(EC.SHAPES) + len(EC.BIG_SHAPES)
+    assert max(max(v) for v in EC.SHAPES.values()) == 80 and min(max(v) for v in EC.BIG_SHAPES.values()) == 81
+    assert max(max(v) for v in EC.BIG_SHAPES.values()) == 256  # (batch creation refuses 257)
+    tiles = lambda n: (n * (n + 1) // 2 + 127) // 128  # noqa: E731
+    assert tiles(127) == 64 and tiles(128) == 65  # 64 pair tiles of 128 pairs, then a 65th
+    assert max(EC.BIG_SHAPES["193+"]) == 193 and EC.BIG_SHAPES["ragged256"] == [1, 255, 2, 80, 3]
+    # the edge coordinates' special rows reach the big shapes too
+    x = EC.frac_coords(EC.BIG_SHAPES["128"], "edge")
+    assert (x[0] == 0).all() and (x[125] == np.float32(EC.LAST)).all() and (x[126] == x[124]).all()
+
+
+def test_reference_blocks_tile_the_nodes_and_do_not_change_the_reference(monkeypatch):
+    """ref64 / base32 run per block of source nodes: the blocks tile nodes and edge rows in order, hold at most
+    REF_BLOCK_ROWS rows, every shape of SHAPES is a single block (its reference is computed as it always was), and
+    a reference cut into many blocks equals the one-block reference to float64 rounding."""
+    for nat in EC.ALL_SHAPES.values():
+        blocks = EC.node_blocks(nat)
+        n = EC.node_counts(nat)
+        assert blocks[0][0] == 0 and blocks[0][2] == 0 and blocks[-1][1] == len(n) and blocks[-1][3] == int(n.sum())
+        for (a, b, r0, r1), nxt in zip(blocks, blocks[1:] + [None]):
+            assert a < b and r1 - r0 == int(n[a:b].sum()) and r1 - r0 <= EC.REF_BLOCK_ROWS
+            assert nxt is None or (nxt[0] == b and nxt[2] == r1)
+    assert all(len(EC.node_blocks(nat)) == 1 for nat in EC.SHAPES.values())
+    assert len(EC.node_blocks(EC.BIG_SHAPES["256"])) == 4 and len(EC.node_blocks(EC.BIG_SHAPES["ragged256"])) > 4
+    nat = [23, 7, 1, 30]
+    w = EC.layer_weights(_sd(), 0)
+    frac, PQ = EC.frac_coords(nat), EC.pq("rowscale", sum(nat), 2)
+    for pairs in (False, True):
+        ref, b32 = EC.ref64(nat, frac, PQ, w, pairs), EC.base32(nat, frac, PQ, w, pairs)
+        with monkeypatch.context() as m:
+            m.setattr(EC, "REF_BLOCK_ROWS", 100)
+            assert len(EC.node_blocks(nat)) > 10
+            cut, cut32 = EC.ref64(nat, frac, PQ, w, pairs), EC.base32(nat, frac, PQ, w, pairs)
+        assert EC.max_row_error(cut, ref) <= 2.0 ** -48
+        assert EC.max_row_error(cut32, ref) <= 2 * EC.max_row_error(b32, ref)  # (another GEMM shape, the same chain)
+
+
+def test_big_shape_families_stay_finite():
+    nat = EC.BIG_SHAPES["81"]
+    w = EC.layer_weights(_sd(), 0)
+    frac = EC.frac_coords(nat)
+    for family in ("normal", "rowscale"):
+        PQ = EC.pq(family, sum(nat), 2)
+        ref, b32 = EC.ref64(nat, frac, PQ, w, True), EC.base32(nat, frac, PQ, w, True)
+        assert np.isfinite(ref).all() and np.isfinite(b32).all()
+        assert EC.max_row_error(b32, ref) <= 64 * EC.U
 
 
 @pytest.mark.parametrize("family", ["chunkdead", "large", "rowscale"])

@@ -18,6 +18,11 @@ same reason the schedules fall into two groups, directed and pairs, each bit-ide
 Guards: d_agg is followed by 8 sentinel rows that must stay untouched, d_PQ by NaN rows inside its allocation, and
 outputs must be finite. A HIP error from the hook ends the session: nothing else runs on the device after a fault.
 
+Crystals of 81 to 256 atoms (EC.BIG_SHAPES, the rest of the range a fully connected batch accepts) run through the
+same tests in cases of their own (test_accuracy_big, test_schedules_big, ...): the second pass of the pair grid's
+flag polling (128 atoms: 65 pair tiles), lists whose pair ranges all start at pair tile 0, nodes cut by a tile edge
+at every offset (255) and nodes of exactly one row tile (256). Their table: profiles/big_crystals/README.md.
+
 Findings: see profiles/r8/edge_unit/README.md."""
 
 import functools
@@ -86,7 +91,7 @@ def _weights(layer):
 @functools.lru_cache(maxsize=None)
 def _case(shape, family, layer, pairs_def, frac_kind="uniform"):
     """(frac, PQ [2, N, 2H], ref64 [2, N, H], the float32 chain's max e per conditioning count {1, 2}), computed once."""
-    nat = EC.SHAPES[shape]
+    nat = EC.ALL_SHAPES[shape]
     frac = EC.frac_coords(nat, frac_kind)
     PQ = EC.pq(family, sum(nat), 2)
     w = _weights(layer)
@@ -166,6 +171,43 @@ def test_accuracy_coincident_atoms_and_cell_edges(dec, math, shape):
         check_gate(f"{math} {shape} edge coordinates pairs {pairs}", agg, ref[:pairs], base[pairs])
 
 
+BIG = list(EC.BIG_SHAPES)
+
+
+@pytest.mark.parametrize("shape", BIG)
+def test_accuracy_big(dec, shape):
+    """Crystals of 81 to 256 atoms on split16's default schedule (the pair grid from 256 row tiles, i.e. at 256 and
+    ragged256; two launches below): layers 0 and L-1, one and two conditionings, under the same gate."""
+    configure(dec, "split16")
+    nat = EC.BIG_SHAPES[shape]
+    for layer in (0, L - 1):
+        frac, PQ, ref, base = _case(shape, "rowscale", layer, True)
+        for pairs in (1, 2):
+            agg, _ = run_layer(dec, nat, pairs, layer, frac, PQ)
+            check_gate(f"split16 {shape} rowscale layer {layer} pairs {pairs}", agg, ref[:pairs], base[pairs])
+
+
+@pytest.mark.parametrize("shape", ["128", "256"])
+@pytest.mark.parametrize("math", ["bf16x3", "f32"])
+def test_accuracy_big_directed_maths(dec, math, shape):
+    configure(dec, math)
+    nat = EC.BIG_SHAPES[shape]
+    frac, PQ, ref, base = _case(shape, "normal", 0, False)
+    for pairs in (1, 2):
+        agg, _ = run_layer(dec, nat, pairs, 0, frac, PQ)
+        check_gate(f"{math} {shape} normal layer 0 pairs {pairs}", agg, ref[:pairs], base[pairs])
+
+
+@pytest.mark.parametrize("shape", ["128", "ragged256"])
+def test_accuracy_big_coincident_atoms_and_cell_edges(dec, shape):
+    configure(dec, "split16")
+    nat = EC.BIG_SHAPES[shape]
+    frac, PQ, ref, base = _case(shape, "normal", 0, True, "edge")
+    for pairs in (1, 2):
+        agg, _ = run_layer(dec, nat, pairs, 0, frac, PQ)
+        check_gate(f"split16 {shape} edge coordinates pairs {pairs}", agg, ref[:pairs], base[pairs])
+
+
 # ---------------------------------------------------------------- schedules (split16)
 
 # option sets of tests/test_gpu_parity.py (test_edge_row_tiles_are_bit_identical, test_edge_pairs_grid_is_bit_identical,
@@ -189,13 +231,52 @@ PAIRS = [
 NO_EVENTS = ("layer_wait_timeouts", "layer_repairs", "tail_wait_timeouts", "tail_repairs", "layer_incomplete")
 
 
+def grid_launches(opts, nat):
+    """One-grid launches a call records under `opts` (decoder.hip edge_plan): the pair grid runs when edge layer 1
+    is on pairs, the one-grid form and row tiles are on and the batch has edge_layer_min row tiles."""
+    o = {**DEFAULTS, **opts}
+    R = (sum(n * n for n in nat) + 255) // 256
+    return int(bool(o["edge_pairs"] and o["edge_pairs_layer"] and o["edge_rows"] and o["edge_layer"]
+                    and R >= o["edge_layer_min"]))
+
+
+def short_tiles_of(nat, pairs, opts):
+    """The mixed tiling batch creation must choose under `opts` (batch.hip short_row_tiles, through the CPU hook
+    tests/test_row_tiles.py checks): -1 unless the options take 192-row tiles at all."""
+    o = {**DEFAULTS, **opts}
+    if not (o["edge_rows"] and o["edge_rows_short"]):
+        return -1
+    import ctypes
+    arr = (ctypes.c_int32 * len(nat))(*nat)
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    return _lib.load().chm_debug_short_row_tiles(arr, len(nat), pairs, ncu, o["edge_layer_min"])
+
+
 @pytest.mark.parametrize("pairs", [1, 2])
 @pytest.mark.parametrize("shape", list(EC.SHAPES))
 @pytest.mark.parametrize("group", ["directed", "pairs"])
 def test_schedules(dec, group, shape, pairs):
     """Every schedule's agg passes the float64 gate and equals the group's first bit for bit; the device counters
     show no timeout and no repair; the schedule that was asked for is the one that ran."""
-    nat = EC.SHAPES[shape]
+    check_schedules(dec, group, shape, pairs)
+
+
+@pytest.mark.parametrize("pairs", [1, 2])
+@pytest.mark.parametrize("shape", ["128", "193+", "256", "ragged256"])
+@pytest.mark.parametrize("group", ["directed", "pairs"])
+def test_schedules_big(dec, group, shape, pairs):
+    """The same on crystals above 80 atoms. From 256 row tiles (256, ragged256) the pair grid is the default, so it
+    runs under every option set that leaves it on, not only under the one that lowers edge_layer_min; the launch
+    count asserted follows that rule (grid_launches). A batch with a crystal above 192 atoms (193+, 256, ragged256)
+    never takes 192-row tiles; 128 takes what batch creation's rule gives an option set that asks for them: with
+    one conditioning 86 short tiles (172 jobs) fit one round of the CUs, with two (344 jobs) they do not, and its
+    64 uniform tiles then fill that round exactly."""
+    check_schedules(dec, group, shape, pairs)
+
+
+def check_schedules(dec, group, shape, pairs):
+    nat = EC.ALL_SHAPES[shape]
+    big = shape in EC.BIG_SHAPES
     layer = L - 1
     frac, PQ, ref, base = _case(shape, "rowscale", layer, group == "pairs")
     lib = _lib.load()
@@ -211,7 +292,17 @@ def test_schedules(dec, group, shape, pairs):
             n_grid = _lib.prof_read(_lib.K_EDGE_LAYER)[0]
             tag = f"{name} | {shape} pairs {pairs}"
             assert all(ev[k] == 0 for k in NO_EVENTS), (tag, ev)
-            assert (short >= 0) == want_short, f"{tag}: chm_batch_short_row_tiles {short}"
+            if not big:
+                assert (short >= 0) == want_short, f"{tag}: chm_batch_short_row_tiles {short}"
+                assert grid_launches(opts, nat) == want_grid
+            elif max(nat) > 192:
+                assert short < 0, f"{tag}: chm_batch_short_row_tiles {short} with a crystal above 192 atoms"
+            else:
+                assert short == (short_tiles_of(nat, pairs, opts) if want_short else -1), \
+                    f"{tag}: chm_batch_short_row_tiles {short}"
+                if pairs == 1:  # (the option's own wish holds where one round takes the short tiles)
+                    assert (short >= 0) == want_short, f"{tag}: chm_batch_short_row_tiles {short}"
+            want_grid = grid_launches(opts, nat)
             assert n_grid == want_grid, f"{tag}: {n_grid} one-grid launches"
             if want_grid:
                 assert ev["layer_other_xcd"] == 0, (tag, ev)
@@ -270,11 +361,23 @@ def test_mean_of_equal_messages(math):
 def test_rows_do_not_depend_on_their_neighbours(dec, opts):
     """Two crystals swapped in natoms, their coordinates and PQ rows moved along: agg's rows move bit for bit, though
     the tiles cut the batch elsewhere."""
+    check_swapped_crystals(dec, opts, EC.SHAPES["ragged5"])  # [23, 7, 40, 1, 80]
+
+
+@pytest.mark.parametrize("opts", [dict(), dict(edge_pairs=1, edge_pairs_layer=1, edge_layer_min=1)],
+                         ids=["default", "pair-grid"])
+def test_rows_do_not_depend_on_their_neighbours_big(dec, opts):
+    """The same with crystals of 130 and 200 atoms (223 row tiles): the 200-atom crystal's nodes, each most of a row
+    tile, meet the tile edges at other offsets once the 7-atom and 1-atom crystals change places."""
+    check_swapped_crystals(dec, opts, [130, 7, 200, 1])
+
+
+def check_swapped_crystals(dec, opts, nat):
     configure(dec, "split16", **opts)
-    nat = EC.SHAPES["ragged5"]  # [23, 7, 40, 1, 80]
     N = sum(nat)
     off = np.concatenate([[0], np.cumsum(nat)])
-    order = [0, 3, 2, 1, 4]  # crystals 1 and 3 swapped
+    order = list(range(len(nat)))
+    order[1], order[3] = 3, 1  # crystals 1 and 3 swapped
     perm = np.concatenate([np.arange(off[g], off[g + 1]) for g in order])
     frac, PQ = EC.frac_coords(nat), EC.pq("rowscale", N, 2)
     a0, _ = run_layer(dec, nat, 2, 0, frac, PQ)
@@ -284,15 +387,15 @@ def test_rows_do_not_depend_on_their_neighbours(dec, opts):
 
 # ---------------------------------------------------------------- split agg rows (pre-split node GEMMs)
 
-@pytest.mark.parametrize("family", ["rowscale", "chunkdead"])
-@pytest.mark.parametrize("shape", ["mixed7", "ragged5", "1"])
+@pytest.mark.parametrize("shape,family", [(s, f) for s in ["mixed7", "ragged5", "1"] for f in ["rowscale", "chunkdead"]]
+                         + [("256", "rowscale")])
 def test_split_agg_rows(dec, shape, family):
     """Option node_ps: the layer writes agg as split rows + packed chunk exponents. Per 128-column chunk
     |(hi + lo) 2^e - agg_fp32| <= 2^-22 max|chunk|: the scaled value is below 1, hi is off by at most 2^-12, lo keeps
     11 more bits or bottoms out at 2^-25, in all 2^-23 2^e, and 2^e <= 2 max. e is the frexp exponent of the chunk's
     maximum (store_split_row512's layout); a dead chunk has exponent 0 and all-zero halves."""
     configure(dec, "split16", node_ps=1)
-    nat = EC.SHAPES[shape]
+    nat = EC.ALL_SHAPES[shape]
     N = sum(nat)
     frac, PQ = EC.frac_coords(nat), EC.pq(family, N, 2)
     w = _weights(0)

@@ -536,6 +536,56 @@ def test_decoder_large_ragged_vs_oracle(model1000, cn):
             close(latt[c].cpu(), rl, what=f"{math} lattice c={c}")
 
 
+def test_decoder_above_128_atoms_vs_oracle(model1000, cn):
+    """Crystals of 129 and 97 atoms between 1 and 3 (the reference workload stops at 80; a fully connected batch
+    takes up to 256), both conditionings, against the CPU oracle under the tolerance of
+    test_decoder_large_ragged_vs_oracle. Which schedule ran is read from the profiling counters and asserted: at
+    its 102 row tiles the batch is below edge_layer_min (256), so every math mode's default is the two-launch form
+    (no one-grid launch recorded); split16 then runs once more with edge_layer_min 1, where the pair grid must
+    record one launch per layer. There the 129-atom crystal's last row tile reads 66 pair tiles, so its jobs'
+    flag polling takes its second pass; no wait may time out, no job be repaired or find another XCD's tiles."""
+    nat = [129, 1, 97, 3]
+    B, N = len(nat), sum(nat)
+    g = torch.Generator().manual_seed(23)
+    a = torch.randint(0, 104, (N,), generator=g)
+    x = torch.rand(N, 3, generator=g)
+    lat = torch.randn(B, 3, 3, generator=g) * 4
+    te = model1000.time_embed(torch.full((B,), 321, dtype=torch.long))
+    dec = model1000.decoder
+    sd = {k: v.detach().cpu() for k, v in dec.state_dict().items()}
+    nat_t = torch.tensor(nat)
+    n2g = torch.arange(B).repeat_interleave(nat_t)
+    refs = [O.cspnet_forward(sd, default_config(), a, x, lat, nat_t, n2g, te, text.expand(B, -1)) for text in cn]
+    L = default_config()["num_layers"]
+    lib = _lib.load()
+    _lib.check(lib.chm_prof_enable(1), "chm_prof_enable")
+    try:
+        for math, layer_min, want_grid in [(m, 256, 0) for m in MATHS] + [("split16", 1, L)]:
+            dec.set_math(math)
+            dec.set_option("edge_layer_min", layer_min)
+            _lib.prof_events(reset=True)
+            _lib.check(lib.chm_prof_reset(), "chm_prof_reset")
+            types, latt, coords, nodes = dec.forward_cfg(a.to(DEV), x.to(DEV), lat.to(DEV), nat_t.to(DEV), te.to(DEV),
+                                                         cn[0].expand(B, -1).to(DEV), cn[1].expand(B, -1).to(DEV),
+                                                         need_nodes=True)
+            torch.cuda.synchronize()
+            ev = _lib.prof_events()
+            n_grid, n_two = _lib.prof_read(_lib.K_EDGE_LAYER)[0], _lib.prof_read(_lib.K_EDGE_MESSAGE)[0]
+            what = f"{math} edge_layer_min {layer_min}"
+            print(f"{what}: {n_grid} one-grid launches, {n_two} layer-2 launches of the two-launch form; events {ev}")
+            assert n_grid == want_grid and n_two == L - want_grid, (what, n_grid, n_two)
+            assert ev["layer_wait_timeouts"] == 0 and ev["layer_repairs"] == 0 and ev["layer_other_xcd"] == 0, (what, ev)
+            for c, (rt, rl, rc, rh) in enumerate(refs):
+                close(nodes[c].cpu(), rh, what=f"{what} nodes c={c}")
+                close(types[c].cpu(), rt, what=f"{what} types c={c}")
+                close(coords[c].cpu(), rc, what=f"{what} coords c={c}")
+                close(latt[c].cpu(), rl, what=f"{what} lattice c={c}")
+    finally:
+        dec.set_option("edge_layer_min", 256)  # (the default)
+        lib.chm_prof_enable(0)
+        lib.chm_prof_reset()
+
+
 @pytest.mark.parametrize("lat_scale", [300.0, 3000.0])
 def test_decoder_wide_range_vs_oracle(model1000, cn, lat_scale):
     """Lattices 300x / 3000x the usual scale (vec(LL^T) up to ~1e8): the lattice term reaches P,
@@ -635,12 +685,12 @@ def test_philox_shard_invariance(model100, cn):
         assert torch.equal(cat, full[k]), f"state {k} differs between 1 and 2 shards"
 
 
-@pytest.mark.parametrize("lanes", [1, 2, 3])
-def test_graph_replay_matches_eager(model100, cn, lanes):
+@pytest.mark.parametrize("nat,lanes", [pytest.param([5, 9, 3, 12, 7, 1, 20], k, id=str(k)) for k in (1, 2, 3)]
+                         + [pytest.param([130, 3, 90], 1, id="130-3-90-1")])
+def test_graph_replay_matches_eager(model100, cn, nat, lanes):
     """One captured reverse step replayed per timestep (device-side t) gives
     bit-identical states to eager stepping, also with the crystals split over
-    concurrent stream lanes inside the graph."""
-    nat = [5, 9, 3, 12, 7, 1, 20]
+    concurrent stream lanes inside the graph, and (one lane) with crystals of 130 and 90 atoms."""
     runs = []
     for graph in (False, True):
         states = list(model100.sample_states(nat, None, 2.0, 1e-5, noise="philox", seed=11, text_embeds=cn[0],
@@ -712,7 +762,7 @@ def test_large_batch_step_is_finite(model1000, cn):
 
 
 # --------------------------------------------------------------------------- edge layer 1 on pairs
-@pytest.mark.parametrize("nat", [[3, 5, 8, 1, 40, 17, 2, 80], [40] * 64])
+@pytest.mark.parametrize("nat", [[3, 5, 8, 1, 40, 17, 2, 80], [40] * 64, [130, 3, 90]])
 def test_edge_pairs_match_directed_edges(model1000, cn, nat):
     """Option edge_pairs: edge layer 1 once per unordered pair (the reverse edge's Fourier features are the
     forward ones with the sine half negated). Its decoder outputs agree with the directed form to within fp32

@@ -168,7 +168,11 @@ def test_every_kind_is_planted_and_read():
         kinds |= {C.KINDS[int(v)] for v in a[:6] if int(v) < 6}
         assert not C.kind_mask(name, 2, "big_mean")[1].any()
     assert kinds == set(C.KINDS)
-    assert sum(C.SHAPES["odd"]) % 4 and sum(C.SHAPES["odd"]) % 2 and max(sum(s) for s in C.SHAPES.values()) == 80
+    assert sum(C.SHAPES["odd"]) % 4 and sum(C.SHAPES["odd"]) % 2
+    # up to the largest crystal a fully connected batch takes, alone and in a ragged batch
+    assert max(max(s) for s in C.SHAPES.values()) == 256 and C.SHAPES["256"] == [256]
+    assert C.SHAPES["big_ragged"] == [1, 255, 2] and max(sum(s) for s in C.SHAPES.values()) == 258
+    assert list(C.SHAPES)[:5] == ["1", "123", "unroll", "odd", "80"]  # (a case's planted kinds rotate by its position)
 
 
 def test_split_rows_model():

@@ -12,6 +12,10 @@ import pytest
 from chemeleon_amd import _lib
 
 PBM, BM = 128, 256
+# crystals of 81 to 256 atoms (the library's own range; the reference workload stops at 80): [127] / [128] bracket
+# the 64 pair tiles one polling pass of a layer-2 job covers, [255] / [256] the row tile's height
+BIG = [[127], [128], [256], [255], [1, 255, 2, 80, 3], [193, 20, 20], [200, 56, 256],
+       list(np.random.default_rng(12).integers(1, 257, 12))]
 
 
 def plan(nat, P=2, lag=10):
@@ -41,7 +45,7 @@ def pair_index(nat):
 
 
 @pytest.mark.parametrize("nat", [[40] * 64, [23, 7, 40, 1, 80] * 23, [1] * 300 + [2] * 70 + [3] * 9, [5, 9, 3],
-                                 [80] * 9, [40] * 512, list(np.random.default_rng(7).integers(1, 81, 256))])
+                                 [80] * 9, [40] * 512, list(np.random.default_rng(7).integers(1, 81, 256))] + BIG)
 def test_pair_plan_covers_every_row_tile_with_its_pairs(nat):
     nat = [int(n) for n in nat]
     P = 2
@@ -90,8 +94,27 @@ def test_pair_plan_covers_every_row_tile_with_its_pairs(nat):
     assert (counts == 2 * P).all()
 
 
+def test_big_crystals_reach_the_paths_they_are_chosen_for():
+    """One crystal of 128 atoms has 8256 pairs = 65 pair tiles, and its last row tile reads all of them: a layer-2
+    job's flag polling (64 flags per pass) takes a second pass with one live lane. 127 atoms (8128 pairs, 64 tiles)
+    is the largest crystal that stays at one pass. For one crystal of 256 atoms every list's pair range starts at
+    pair tile 0 (the row tile's first crystal's first pair tile), so neighbouring lists share most of their pair
+    tiles instead of one or two."""
+    def widths(nat):
+        rng = plan(nat)[0]
+        return rng[:, 1] - rng[:, 0] + 1
+    assert widths([127]).max() == 64
+    w = widths([128])
+    assert w.max() == 65 and (w > 64).sum() >= 1
+    assert max(widths(n).max() for n in ([80], [23, 7, 40, 1, 80] * 23, [80] * 9)) <= 64  # (the 1..80 range never did)
+    rng, pa, pb, nj, _, R = plan([256])
+    assert R == 256 and (nj > 0).all() and (pa == 0).all()
+    assert (np.diff(pb) > 0).all() and pb[-1] == 257 and (rng[:, 1] - rng[:, 0] + 1).max() == 257
+    assert min(pb[:-1]) > 8  # neighbouring lists share tens of pair tiles
+
+
 @pytest.mark.parametrize("nat", [[40] * 64, [23, 7, 40, 1, 80] * 23, [1] * 300 + [2] * 70 + [3] * 9, [5, 9, 3],
-                                 [80] * 9, [79, 78, 2, 80], list(np.random.default_rng(7).integers(1, 81, 256))])
+                                 [80] * 9, [79, 78, 2, 80], list(np.random.default_rng(7).integers(1, 81, 256))] + BIG)
 def test_pair_tile_node_ranges_cover_their_pairs(nat):
     """The node range each pair tile's epilogue stages (chm_debug_pair_nodes, batch creation): every node i and j
     of the tile's pairs lies inside it, and it starts at the tile's first node (no row is staged below it)."""

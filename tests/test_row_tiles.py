@@ -65,7 +65,7 @@ MIXED = [([20] * 64, 64), ([20] * 64, 0), ([20] * 64, 99), ([40] * 16, 10), ([6]
 
 @pytest.mark.parametrize("natoms", [
     [40] * 64, [20] * 64, [6] * 4, [80] * 9, [1] * 600, [16] * 16, [256], [1, 255, 2, 80, 3],
-    np.random.default_rng(7).integers(1, 81, 300).tolist(),
+    np.random.default_rng(7).integers(1, 81, 300).tolist(), [255], [193, 20, 20],
 ])
 def test_row_tiles_match_direct_construction(natoms):
     check_tiles(natoms, -1)
@@ -123,7 +123,7 @@ def reference_nodes(natoms, nbig=-1):
 
 @pytest.mark.parametrize("natoms", [
     [40] * 64, [20] * 64, [6] * 4, [80] * 9, [1] * 600, [16] * 16, [256], [1, 255, 2, 80, 3],
-    np.random.default_rng(7).integers(1, 81, 300).tolist(),
+    np.random.default_rng(7).integers(1, 81, 300).tolist(), [255], [193, 20, 20],
 ])
 def test_row_tile_node_lists(natoms):
     """The host-built node lists (chm_debug_row_nodes, the table edge layer 2's epilogue reads) equal the
@@ -183,6 +183,9 @@ def test_row_tiles_reject_bad_batches():
     ([20] * 40, 2, 256, 256, -1),     # 252 jobs (98%): the short tiles would need 268 jobs
     ([193] + [20] * 63, 2, 256, 256, -1),  # a crystal above 192 atoms
     ([20] * 64, 2, 0, 256, -1),       # no CU count
+    # (the bracketing pair of the 192-atom rule; appended, so the cases above keep their ids)
+    ([192], 2, 256, 256, 128),        # 144 row tiles = 576 jobs: two full rounds + 22 short tiles
+    ([193], 2, 256, 256, -1),         # 146 row tiles, the same rounds: refused for the crystal's size alone
 ])
 def test_short_row_tiles_choice(natoms, P, ncu, lmin, want):
     """The mixed tiling a batch takes (chm_debug_short_row_tiles, the rule batch creation applies): 256-row tiles
@@ -195,3 +198,19 @@ def test_short_row_tiles_choice(natoms, P, ncu, lmin, want):
         E = sum(n * n for n in natoms)
         R = got + (E - 256 * got + 191) // 192
         assert (R - got) * 2 * P <= ncu and 256 * got < E
+
+
+@pytest.mark.parametrize("natoms", [[193], [256], [193, 20, 20], [20] * 30 + [200], [6, 255, 6], [1, 255, 2, 80, 3],
+                                    [200, 56, 256]])
+def test_short_row_tiles_are_refused_above_192_atoms(natoms):
+    """A node of a crystal above 192 atoms can span three 192-row tiles, which the tile table (one continued node
+    per tile) cannot express: whatever the conditionings, CU count and edge_layer_min, such a batch keeps uniform
+    tiles. The same batch with that crystal at 192 atoms takes short tiles for at least one of these settings."""
+    lib = _lib.load()
+    settings = [(P, ncu, lmin) for P in (1, 2) for ncu in (64, 256, 304, 1024) for lmin in (256, 1000, 1 << 20)]
+
+    def choices(nat):
+        arr = (ctypes.c_int32 * len(nat))(*nat)
+        return [lib.chm_debug_short_row_tiles(arr, len(nat), P, ncu, lmin) for P, ncu, lmin in settings]
+    assert all(c == -1 for c in choices(natoms))
+    assert any(c >= 0 for c in choices([min(n, 192) for n in natoms]))
