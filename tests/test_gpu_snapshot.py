@@ -1,4 +1,5 @@
-"""Streaming output on the device: k_state_snapshot against the host path (schema.step_to_atoms), the
+"""Streaming output on the device: k_state_snapshot against the host path (schema.step_to_atoms), for crystals of
+up to 130 atoms and for crystals around and above the 1024 sort keys the kernel stages at a time, the
 argument checks and graph capture of chm_snapshot_run, and the overlapped generator
 (_sample_generator(overlap=True) over schema.StateStreamer) against the blocking one, step by step and
 exactly."""
@@ -21,6 +22,10 @@ pytestmark = [pytest.mark.gpu,
 DEV = "cuda"
 NATOMS = [1, 2, 63, 64, 65, 130, 7]  # one atom, around the wave width, two and three passes of the wave
 POOL = [0, 1, 2, 6, 17, 20, 103, 104, 500]  # X, H, He, C, Cl, Ca, Lr and two classes the clamp sends to X
+# above the 1024 keys the kernel stages at a time: one key short of a chunk, a full chunk, one more (two stagings per
+# 64 atoms), a small crystal between them, and three stagings with a tail that is no multiple of 4 or 64
+NATOMS_BIG = [1023, 1024, 1025, 3, 2113]
+NEGATIVE = -7  # a class the sampler never produces: the kernel clamps it to X, step_to_atoms refuses it
 
 
 def same_structures(got, want):
@@ -62,6 +67,22 @@ def seeded_state(natoms, seed):
     return a, torch.rand(N, 3, generator=g), torch.randn(B, 3, 3, generator=g)
 
 
+def seeded_state_big(seed):
+    """NATOMS_BIG: the pool and the negative class, and in every crystal that has them atoms 1000 to 1100 (or to its
+    end) of one element, so that equal symbols lie on both sides of a chunk boundary."""
+    N, B = sum(NATOMS_BIG), len(NATOMS_BIG)
+    g = torch.Generator().manual_seed(seed)
+    pool = torch.tensor(POOL + [NEGATIVE])
+    a = pool[torch.randint(0, len(pool), (N,), generator=g)]
+    off = 0
+    for n, element in zip(NATOMS_BIG, (17, 6, 17, 0, 6)):
+        if n > 1000:
+            a[off + 1000:off + min(n, 1100)] = element
+        off += n
+    assert (a == NEGATIVE).sum() > 100
+    return a, torch.rand(N, 3, generator=g), torch.randn(B, 3, 3, generator=g)
+
+
 @pytest.fixture(scope="module")
 def plan():
     p = Plan(NATOMS)
@@ -69,20 +90,32 @@ def plan():
     p.close()
 
 
-def test_kernel_matches_step_to_atoms(plan):
-    a, x, lat = seeded_state(NATOMS, 11)
+@pytest.fixture(scope="module")
+def big_plan():
+    p = Plan(NATOMS_BIG)
+    yield p
+    p.close()
+
+
+@pytest.mark.parametrize("which", ["to_130_atoms", "above_1024_atoms"])
+def test_kernel_matches_step_to_atoms(request, which):
+    big = which == "above_1024_atoms"
+    plan = request.getfixturevalue("big_plan" if big else "plan")
+    NATOMS = plan.natoms
+    a, x, lat = seeded_state_big(11) if big else seeded_state(NATOMS, 11)
     assert plan.slot_bytes == slot_layout(NATOMS)["bytes"]
     slot = torch.zeros(plan.slot_bytes, dtype=torch.uint8, device=DEV)
     ad, xd, ld = a.to(DEV), x.to(DEV), lat.to(DEV)
     assert plan.run(ad, xd, ld, slot) == 0, _lib.load().chm_last_error()
     host = slot.cpu().numpy()
-    same_structures(slot_to_atoms(host, NATOMS), step_to_atoms(a, x, lat, NATOMS))
+    # (step_to_atoms gets the negative class as the X the kernel clamps it to: it refuses a negative number)
+    same_structures(slot_to_atoms(host, NATOMS), step_to_atoms(torch.where(a < 0, 0, a), x, lat, NATOMS))
     # perm: per crystal a permutation that maps the sorted rows to their sources, equal symbols in source order
     lay, N = slot_layout(NATOMS), sum(NATOMS)
     perm = host[lay["perm"]:lay["numbers"]].view(np.int32)
     num = host[lay["numbers"]:lay["numbers"] + N]
     sx = host[lay["frac"]:lay["perm"]].view(np.float32).reshape(N, 3)
-    clamped = torch.where(a <= 103, a, 0).numpy()
+    clamped = torch.where((a >= 0) & (a <= 103), a, 0).numpy()
     off = 0
     for n in NATOMS:
         p = perm[off:off + n]
@@ -91,6 +124,9 @@ def test_kernel_matches_step_to_atoms(plan):
         np.testing.assert_array_equal(sx[off:off + n], x.numpy()[off:off + n][p])
         same = num[off + 1:off + n] == num[off:off + n - 1]
         assert np.all(p[1:][same] > p[:-1][same])
+        if n > 1025:  # the forced run comes out in source order, across the boundary between two stagings
+            run = p[np.isin(p, np.arange(1000, 1100))]
+            assert run.tolist() == list(range(1000, 1100)) and len(set(clamped[off + 1000:off + 1100])) == 1
         off += n
 
 
